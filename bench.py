@@ -6,8 +6,13 @@ in-kernel lattice generation, trilinear gather of the channels-last feature grid
 per-point conditioned ResNet MLP) over one synthetic scene; weights and feature
 grid are resident in HBM when the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
+* A plain run sets up, warms up, times EXACTLY K steps and prints the headline line (value, ms_per_step, the roofline
+  of the timed kernel); ``--dump-outputs DIR`` then writes the logits of the last timed step as ``DIR/logits.npy``
+  (float32, [1, nx^3]; a fixed seeded sample above 8M points).  The inputs are seeded: identical from run to run.
+* ``--full`` adds everything else the line has carried: the other precisions' kernels, the sections below and the
+  CPU baseline (each in runs of its own, after the headline).
 * ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment: this process touches no GPU and starts
   N ranks (``python -m torch.distributed.run``, one process per GPU, RCCL) of itself; under a launcher
   (WORLD_SIZE set) ``--gpus`` must agree with it.
@@ -15,7 +20,7 @@ grid are resident in HBM when the timed region starts.
   no data-path collective -- value = N * nx^3 * steps / max-over-ranks time.
   ``--scaling strong``: ONE scene, every rank decodes its slab of the lattice (whole x-plane pairs) and one
   all-gather rebuilds the value grid on every rank; value = nx^3 * steps / time (N = 1: the same number).
-* Unless ``--decode-only``: the same JSON line carries ``sharded_scene`` (BASELINE config 5's shape of work:
+* With ``--full`` and unless ``--decode-only``: the same JSON line carries ``sharded_scene`` (BASELINE config 5's shape of work:
   redundant encode, slab decode, one all-gather, marching cubes on rank 0; at 128^3 and 256^3) and
   ``train_step`` (config 4: the VTacO training step, 8 scenes x 2048 points per GPU, bucketed gradient
   all-reduce over RCCL overlapped with backward; ms/step and the all-reduce's share), and at N = 1 the
@@ -43,7 +48,8 @@ KERNEL_OF = {"f32": "decode_fwd_staged2_kernel<0>", "bf16x3": "decode_fwd_staged
              "f16f8": "decode_fwd_staged3_kernel<2>"}
 SPLIT = ("bf16x3", "f16x3", "f16f8")   # dense layers on the 16-bit matrix core, operands as hi + lo
 MIN_WARM_S = 0.25             # launches before any timed region, whatever --warmup says (clocks settle)
-MIN_TIMED_S = 0.05            # the timed region is REPS x --steps steps, REPS chosen so that it lasts at least this long
+MIN_TIMED_S = 0.05            # a side kernel's timed region (--full) is REPS x --steps steps, REPS chosen so that it lasts at least this long
+DUMP_MAX_POINTS = 1 << 23     # --dump-outputs: logits written whole up to this many points (32 MB), a seeded sample beyond
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -152,6 +158,20 @@ def mesh_extract_stats(vol, nx, runs=100):
     return {"p50_ms": p50, "p90_ms": lat[int(len(lat) * 0.9)], "min_ms": lat[0], "runs": runs, "verts": v.shape[0],
             "faces": f.shape[0], "level": lvl, "algorithmic_GBps": nbytes / (p50 * 1e-3) / 1e9,
             "note": "latency-dominated (five dependent launches, the counts polled from a page-locked slot); 8.4 MB volume = 1.3 us at HBM rate"}
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: the logits of the timed path's last step as a caller of decode_lattice receives them ([1, nx^3] f32) in
+    path/logits.npy; beyond DUMP_MAX_POINTS a fixed seeded sample of them (the same points on every run) in path/logits_sample.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    vals, name = out.detach().float().cpu(), "logits"
+    if vals.numel() > DUMP_MAX_POINTS:
+        idx = torch.randint(0, vals.numel(), (DUMP_MAX_POINTS,), generator=torch.Generator().manual_seed(0)).sort().values
+        vals, name = vals.reshape(-1)[idx], "logits_sample"
+    np.save(os.path.join(path, name + ".npy"), vals.numpy())
+    return name
 
 
 def stage_times(scene, dec, grid, nx, out, dev, precision):
@@ -358,23 +378,25 @@ def clock_of_last_launch(vops):
     return c
 
 
-def timed_region(step, steps, fx, collective=False):
+def timed_region(step, steps, fx, collective=False, reps=None):
     """The timed region of one kernel: REPS back-to-back repetitions of EXACTLY `steps` steps between two barrier +
-    synchronize fences, REPS = the smallest count that makes the region last MIN_TIMED_S (a 20-step region of this kernel is
-    ~3 ms: the fences' own ~0.3 ms was a tenth of it in round 3's record).  One HIP event per repetition on the launch stream
-    gives the per-repetition kernel time: their spread is in the line.  Returns (wall seconds max over ranks, timed steps,
-    stats of the per-repetition ms per step)."""
+    synchronize fences.  `reps` given (the headline: 1, so that --steps is the number of timed steps): that many; otherwise
+    the smallest count that makes the region last MIN_TIMED_S (a 20-step region of this kernel is ~3 ms: the fences' own
+    ~0.3 ms was a tenth of it in round 3's record).  One HIP event per repetition on the launch stream gives the
+    per-repetition kernel time: their spread is in the line.  Returns (wall seconds max over ranks, timed steps, stats of
+    the per-repetition ms per step)."""
     import math
     import torch
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(8):
-        step()
-    torch.cuda.synchronize()
-    est = (time.perf_counter() - t0) / 8
-    if collective or fx.dist is not None:
-        est = fx.max_over_ranks(est)                       # every rank times the SAME number of steps (value = all ranks' units / max time)
-    reps = max(1, min(4096, int(math.ceil(MIN_TIMED_S / max(est * steps, 1e-9)))))
+    if reps is None:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(8):
+            step()
+        torch.cuda.synchronize()
+        est = (time.perf_counter() - t0) / 8
+        if collective or fx.dist is not None:
+            est = fx.max_over_ranks(est)                   # every rank times the SAME number of steps (value = all ranks' units / max time)
+        reps = max(1, min(4096, int(math.ceil(MIN_TIMED_S / max(est * steps, 1e-9)))))
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
     fx.fence()
     t0 = time.perf_counter()
@@ -785,8 +807,13 @@ def main():
                          "the fewest shader cycles), or f16 products with fp8 correction products (opt-in: relative error ~3e-5 |logit|)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: one scene per rank, no collective; strong: one scene, slab decode + one all-gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the logits of the last one as DIR/logits.npy (float32; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other precisions' kernels, mesh extract, stage times, the sharded-scene and "
+                         "training-step sections, configs 3 and 5 and the CPU baseline (the options below trim it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--decode-only", action="store_true", help="only the decode metric (perf experiments)")
+    ap.add_argument("--decode-only", action="store_true", help="with --full: only the decode metric and its other precisions")
     ap.add_argument("--no-train", action="store_true", help="skip the config-4 training-step section")
     ap.add_argument("--no-configs35", action="store_true", help="skip the config-3 (full VTacO, 128^3) and config-5 (VTacOH route, 256^3) sections")
     ap.add_argument("--train-scenes", type=int, default=8, help="scenes per GPU of the training-step section (config 4: 8)")
@@ -876,9 +903,10 @@ def main():
 
     from vtaco_amd import ops as vops
     warm_steps = warm_up(step, args.warmup, fx, collective=strong and world > 1)
-    wall, timed_steps, timing = timed_region(step, args.steps, fx, collective=strong and world > 1)
+    wall, timed_steps, timing = timed_region(step, args.steps, fx, collective=strong and world > 1, reps=1)
     kern_ms = timing["kernel_ms_total_events"]          # HIP events on the launch stream, over the whole timed region
     clock = clock_of_last_launch(vops)                  # stamps of the LAST launch: the clock the chip held, ramp and tail
+    dumped = dump_outputs(out, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     res = None
     if rank == 0:
@@ -890,10 +918,9 @@ def main():
             "unit": "query-points/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "warmup_steps_run": warm_steps,
             "ms_per_step": 1e3 * wall / timed_steps,
-            "timing": dict(timing, note="the timed region is `reps` back-to-back repetitions of exactly `steps` steps between ONE pair "
-                                        f"of barrier + synchronize fences (reps = what makes it last >= {MIN_TIMED_S} s); value and "
-                                        "ms_per_step are over all of them (wall clock, max over ranks); kernel_ms_* are HIP-event times "
-                                        "per repetition on the launch stream"),
+            "timing": dict(timing, note="the timed region is exactly `steps` steps between ONE pair of barrier + synchronize fences; "
+                                        "value and ms_per_step are over them (wall clock, max over ranks); kernel_ms_* are the HIP-event "
+                                        "time of the region on the launch stream, per step"),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": args.precision, "data": "synthetic",
             "config": {"workload": f"visual-only PointNet encoder + LocalDecoder, {nx}^3 lattice, "
@@ -912,6 +939,15 @@ def main():
         }
         if not strong or world == 1:
             res["roofline"] = roofline_of(args.precision, flop_pt, npts, kern_ms, clock)
+        if dumped:
+            res["dump_outputs"] = os.path.join(args.dump_outputs, dumped + ".npy")
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    if rank == 0:
         if world == 1 and args.precision in SPLIT:
             # the other kernels on the same inputs: exact f32 (what the training forward and precision="f32" run) and the
             # other split form

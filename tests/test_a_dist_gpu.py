@@ -147,7 +147,7 @@ def test_bench_gpus_2_starts_two_ranks_and_strong_equals_the_lattice():
 
 
 def test_bench_gpus_2_runs_the_multi_rank_sections():
-    """Pre-flight of the driver's scaling run: ``bench.py --gpus 2`` WITHOUT --decode-only (two ranks sharing the one GPU over gloo,
+    """Pre-flight of the driver's scaling run: ``bench.py --gpus 2 --full`` WITHOUT --decode-only (two ranks sharing the one GPU over gloo,
     small knobs) executes the sections that only exist with world > 1 -- the sharded scene's all-gather with every rank's stage
     times, the training step's bucketed gradient all-reduce, its share -- and leaves no ``extras_error``."""
     import json
@@ -158,7 +158,7 @@ def test_bench_gpus_2_runs_the_multi_rank_sections():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, VTACO_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
                           "--train-scenes", "1", "--train-steps", "1", "--sharded-sizes", "128"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -196,8 +196,15 @@ def test_oracle_plane_unet_matches_the_reference_module_golden():
             if name.endswith("bias"):
                 p.copy_(torch.randn(p.shape, generator=g) * 0.05)
     sd = {k: v.detach().clone().requires_grad_(True) for k, v in net.state_dict().items()}
-    for name in sd:
-        assert float(sd[name].detach().double().sum()) == z[f"psum.{name}"][0], name
+    # the fixture's sums were taken with 8 intra-op threads (make_plane_unet_goldens.py): torch's CPU reduction splits a tensor by the
+    # thread count, so a float64 sum is bit-equal to the stored one only under the same count, whatever cores this host has
+    threads = torch.get_num_threads()
+    torch.set_num_threads(8)
+    try:
+        for name in sd:
+            assert float(sd[name].detach().double().sum()) == z[f"psum.{name}"][0], name
+    finally:
+        torch.set_num_threads(threads)
     x = torch.from_numpy(z["x"]).requires_grad_(True)
     out = orc.unet2d_forward(sd, x)
     (out * torch.from_numpy(z["w"])).sum().backward()
@@ -239,24 +246,39 @@ def _g20_check_param_grads(z, tag, grads, tol, sample_seed=G20_SAMPLE_SEED):
     assert seen == sum(1 for k in z if k.startswith(f"{tag}.gsum."))
 
 
-@pytest.mark.parametrize("tag", ["D", "E"])
-def test_oracle_attention_decoder_autograd_matches_the_reference_gradients(tag):
-    """g20 (the REAL reference's autograd through AttentionDecoder.forward_img at c_dim 128 / hidden 256 / 5 blocks and 64 / 64 / 2,
-    make_attn_wide_goldens.py): torch autograd through the oracle's restatement gives the same d grid, d c_img and parameter
-    gradients -- what makes it the checker of the HIP backward at the widths in between (tests/test_fusion_gpu.py)."""
-    import os
-    from conftest import GOLDEN
-    a, sd = load_golden("g17_attention_wide.npz")
-    z = dict(np.load(os.path.join(GOLDEN, "g20_attention_wide_grads.npz")))
+# A ReLU input this close to 0 has no sign in f32: how the BLAS of the host rounds decides it.  Its gate moves the backward by O(1) on
+# that unit (g20 case D: one unit of a decoder block, -4.8e-8 where the fixture was made, +2.6e-8 with AVX2 BLAS kernels; d c_img then
+# differs by 1.6e-2 of its max), while the next-closest input of any ReLU there is 4.2e-7.
+G20_RELU_TIE = 2e-7
+
+
+def _g20_oracle_grads(a, sd, z, tag, flip=()):
+    """Torch autograd through the oracle for g20's case ``tag``: (d grid, d c_img, parameter gradients, ReLU units whose input is within
+    G20_RELU_TIE of 0 as (call, flat index)).  The units in ``flip`` take the other gate in the backward; every forward value is unchanged."""
+    import torch.nn.functional as F
     arrs = {k[2:]: v for k, v in a.items() if k.startswith(tag + ".")}
     sdc = {k[2:]: v.float().requires_grad_(v.dtype.is_floating_point) for k, v in sd.items() if k.startswith(tag + ".")}
     grid = T(arrs["grid"].astype("float32")).requires_grad_(True)
     c_img = T(arrs["c_img"].astype("float32")).requires_grad_(True)
-    out = orc.attention_decoder_forward_img(sdc, T(arrs["p"]), grid, c_img)
+    relu, ties, calls = F.relu, [], [0]
+
+    def tie_aware_relu(x, *args, **kw):
+        y = relu(x, *args, **kw)
+        call, calls[0] = calls[0], calls[0] + 1
+        ties.extend((call, i) for i in (x.detach().abs().reshape(-1) <= G20_RELU_TIE).nonzero().reshape(-1).tolist())
+        mine = [i for c, i in flip if c == call]
+        if mine:
+            m = torch.zeros(x.numel(), dtype=x.dtype)
+            m[mine] = 1.0
+            m = m.reshape(x.shape) * torch.where(x.detach() > 0, -1.0, 1.0).to(x.dtype)
+            y = y + m * (x - x.detach())                  # value + 0, gradient gate 1 <-> 0
+        return y
+    F.relu = tie_aware_relu
+    try:
+        out = orc.attention_decoder_forward_img(sdc, T(arrs["p"]), grid, c_img)
+    finally:
+        F.relu = relu
     (out * T(z[f"{tag}.w"])).sum().backward()
-    for got, key in ((grid.grad, "d_grid"), (c_img.grad, "d_c_img")):
-        ref = T(z[f"{tag}.{key}"])
-        assert float((got - ref).abs().max()) <= 2e-5 * float(ref.abs().max()), (tag, key)
     # the fuser's self-attention unit is ONE module used by its encoder and its decoder layer (TransformerFusion.py:282-296): the
     # reference's named_parameters lists it once, under the encoder's name, with the sum of both uses' gradients
     grads = {k: v.grad for k, v in sdc.items() if v.dtype.is_floating_point and "running" not in k}
@@ -265,4 +287,33 @@ def test_oracle_attention_decoder_autograd_matches_the_reference_gradients(tag):
         enc = k.replace("fuser.decoder.", "fuser.encoder.")
         if g is not None:
             grads[enc] = g if grads[enc] is None else grads[enc] + g
+    return grid.grad, c_img.grad, grads, ties
+
+
+@pytest.mark.parametrize("tag", ["D", "E"])
+def test_oracle_attention_decoder_autograd_matches_the_reference_gradients(tag):
+    """g20 (the REAL reference's autograd through AttentionDecoder.forward_img at c_dim 128 / hidden 256 / 5 blocks and 64 / 64 / 2,
+    make_attn_wide_goldens.py): torch autograd through the oracle's restatement gives the same d grid, d c_img and parameter
+    gradients -- what makes it the checker of the HIP backward at the widths in between (tests/test_fusion_gpu.py).  A ReLU unit whose
+    input has no sign in f32 (G20_RELU_TIE; at most 3 of them) may have taken either gate in the reference: its gates are tried both
+    ways, and one choice must reproduce the fixture within the same bounds."""
+    import itertools
+    import os
+    from conftest import GOLDEN
+    a, sd = load_golden("g17_attention_wide.npz")
+    z = dict(np.load(os.path.join(GOLDEN, "g20_attention_wide_grads.npz")))
+
+    def within(d_grid, d_c_img):
+        return all(float((got - T(z[f"{tag}.{key}"])).abs().max()) <= 2e-5 * float(np.abs(z[f"{tag}.{key}"]).max())
+                   for got, key in ((d_grid, "d_grid"), (d_c_img, "d_c_img")))
+    d_grid, d_c_img, grads, ties = _g20_oracle_grads(a, sd, z, tag)
+    assert len(ties) <= 3, (tag, ties)
+    flips = (f for n in range(1, len(ties) + 1) for f in itertools.combinations(ties, n))
+    for flip in flips:
+        if within(d_grid, d_c_img):
+            break
+        d_grid, d_c_img, grads, _ = _g20_oracle_grads(a, sd, z, tag, flip)
+    for got, key in ((d_grid, "d_grid"), (d_c_img, "d_c_img")):
+        ref = T(z[f"{tag}.{key}"])
+        assert float((got - ref).abs().max()) <= 2e-5 * float(ref.abs().max()), (tag, key, ties)
     _g20_check_param_grads(z, tag, grads, 2e-5)

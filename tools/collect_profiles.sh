@@ -10,7 +10,7 @@ step(){ name=$1; rc=$2; if [ "$rc" != 0 ]; then echo "FAILED: $name rc=$rc"; FAI
 TAG=${TAG:-r06}
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_under_profiler.json 2> $O/stats.err; step stats $?
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 $R/bench.py --steps 100 --warmup 10 --full --no-cpu-baseline > $O/bench_under_profiler.json 2> $O/stats.err; step stats $?
 find $O/stats -name '*kernel_trace*' -delete 2>/dev/null
 # the headline kernel alone (128^3 launches only: the full bench above also decodes 256^3 slabs with the same kernel, which skews its average)
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_decode -o decode -- python3 $R/bench.py --steps 200 --warmup 20 --decode-only --no-cpu-baseline > $O/bench_decode_under_profiler.json 2> $O/stats_decode.err; step "decode stats" $?
@@ -27,7 +27,7 @@ for P in f16x3 f16f8 bf16x3 f32; do
   pmc sq GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES
   pmc sq2 SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAVE_CYCLES
 done
-timeout 300 python3 $R/bench.py > $O/bench.json 2> $O/bench.err; step bench $?
+timeout 300 python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err; step bench $?
 timeout 600 python3 $R/tools/bench_extra.py > $O/bench_extra.jsonl 2> $O/bench_extra.err; step extra $?
 du -sh $O
 exit $FAILED

@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=/root/repo; O=$R/gpurun_out/pmc_conv; mkdir -p $O
 echo "kernel,counter,launches,mean_per_launch" > $O/summary.csv
-pmc(){ tag=$1; shift; d=$O/$tag; timeout 300 rocprofv3 --pmc "$@" --kernel-trace -d $d -o p -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-train > /dev/null 2>&1; echo "pmc $tag rc=$?"
+pmc(){ tag=$1; shift; d=$O/$tag; timeout 300 rocprofv3 --pmc "$@" --kernel-trace -d $d -o p -- python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-train > /dev/null 2>&1; echo "pmc $tag rc=$?"
   python3 $R/tools/pmc_summary.py conv_h8=$d --kernel "conv3d_gcr_hw_kernelILi8E,conv3d_gcr_hw_kernel<8>" | tail -n +2 >> $O/summary.csv
   python3 $R/tools/pmc_summary.py conv_h4=$d --kernel "conv3d_gcr_hw_kernelILi4E,conv3d_gcr_hw_kernel<4>" | tail -n +2 >> $O/summary.csv
   python3 $R/tools/pmc_summary.py conv_s2=$d --kernel "conv3d_gcr_s_kernelILi2E,conv3d_gcr_s_kernel<2>" | tail -n +2 >> $O/summary.csv
