@@ -1051,6 +1051,29 @@ int vt_contact_points(const float *depth, const int *index, const int *sel, cons
                       int n_images, int n_pixels, int width, int height, double fov_deg, int max_points, int S,
                       float *p_sample, long long *finger, void *stream);
 
+/* Evaluation metrics of the visualise block: the reference's generate_obj_mesh_wnf ends with                                   */
+/*   cd = chamfer_distance(points_obj, vertices[:2048], use_kdtree=False); emd = EarthMoverDistance(points_obj[0], vertices)     */
+/* (src/conv_onet/generation.py:274-284; src/common.py:45-51 cdist + scipy linear_sum_assignment, :69-91 the naive Chamfer).      */
+/* vt_chamfer_nn: a [B][N][3], b [B][M][3] f32 -> for every point of a the squared distance to its nearest point of b and that  */
+/*   point's index (d_ab, i_ab [B][N]), and the same from b to a (d_ba, i_ba [B][M]), one launch.  d = (dx*dx + dy*dy) + dz*dz  */
+/*   in f32, unfused (the minima are numpy's f32 restatement bit for bit); equal minima give the smallest index.                 */
+int vt_chamfer_nn(const float *a, const float *b, int B, int N, int M, float *d_ab, int *i_ab, float *d_ba, int *i_ba, void *stream);
+/* vt_emd_auction: the minimum-cost assignment between a [B][N][3] and b [B][M][3] under Euclidean cost (what cdist +          */
+/*   linear_sum_assignment computes), by an epsilon-scaling auction, one workgroup per problem with its state in LDS.  The       */
+/*   smaller side is padded with dummy points of cost 0 to everything, to n = max(N, M) <= VT_EMD_MAX_POINTS (VT_ERR_UNSUPPORTED  */
+/*   beyond).  Outputs per problem: assign [B][n] i32 (person -> object of the padded problem: rows of a, then dummies),        */
+/*   prices [B][n] f32 (the dual prices of the objects), cost_f64 [B] = sum |a_i - b_assign[i]| over the real pairs in float64    */
+/*   (cdist's arithmetic) / N (len(d)), status [B] i32 (0 = converged, 1 = max_rounds Jacobi rounds spent before the last phase  */
+/*   ended: the outputs are not an assignment; the host raises).  Epsilon starts at the cost range / 5, is divided by 5 per phase */
+/*   down to eps_final; the result satisfies eps_final-complementary slackness, so cost <= optimum + n eps_final / N.            */
+/*   ws: NULL or B * vt_emd_workspace_bytes(N, M) bytes that receive per-problem counters {i64 rounds, i64 bids, i32 phases,   */
+/*   f32 last eps, i64 0}.  vt_emd_workspace_bytes returns 0 for sizes the kernel does not cover.                                */
+#define VT_EMD_MAX_POINTS 4096
+#define VT_EMD_WORKSPACE_PER_PROBLEM 32
+size_t vt_emd_workspace_bytes(int n, int m);
+int vt_emd_auction(const float *a, int N, const float *b, int M, int B, float eps_final, int max_rounds,
+                   int *assign, float *prices, double *cost_f64, int *status, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

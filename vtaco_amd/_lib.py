@@ -282,6 +282,9 @@ SIGNATURES = {
     "vt_conv1x1_cl": (_I, [_VP, _I64, _I, _VP, _VP, _I, _VP, _VP]),
     "vt_voxel_scatter_mean_cl_fwd": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP]),
     "vt_voxel_scatter_mean_cl_bwd": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP]),
+    "vt_chamfer_nn": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "vt_emd_workspace_bytes": (_SZ, [_I, _I]),
+    "vt_emd_auction": (_I, [_VP, _I, _VP, _I, _I, _F, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
 }
 
 _lib = None

@@ -25,7 +25,46 @@ from .._lib import VtError
 # the scan kernel writes (ops.mc_count_echo)
 _MC_ECHO = os.environ.get("VTACO_MC_ECHO", "1") != "0"
 
-Mesh = namedtuple("Mesh", ["vertices", "faces"])
+class Mesh(namedtuple("Mesh", ["vertices", "faces"])):
+    """(vertices [V,3], faces [F,3]) as tensors, on the device the generator left them -- a namedtuple (field access, unpacking,
+    equality as a tuple) that also writes itself to a file the way the reference's ``trimesh.Trimesh.export`` is called
+    (train.py:252-253, generate.py): see ``export``."""
+    __slots__ = ()
+
+    FILE_TYPES = ("off", "ply", "obj")
+
+    def export(self, file_obj, file_type=None):
+        """Write the mesh to ``file_obj`` (a path) as OFF, ASCII PLY or OBJ, chosen by ``file_type`` or the path's extension.
+        The vertices and faces are written as given: no duplicate-vertex merging, no removal of degenerate or unreferenced
+        entries (trimesh's ``process=True`` does both).  float32 vertices are printed with 9 significant digits, float64 ones
+        with 17: either reads back to the same value."""
+        import numpy as np
+        ft = (file_type or os.path.splitext(str(file_obj))[1].lstrip(".")).lower()
+        if ft not in self.FILE_TYPES:
+            raise VtError(f"Mesh.export: unknown file type {ft!r} (one of {', '.join(self.FILE_TYPES)})")
+        v = self.vertices.detach().cpu().numpy() if torch.is_tensor(self.vertices) else np.asarray(self.vertices)
+        f = self.faces.detach().cpu().numpy() if torch.is_tensor(self.faces) else np.asarray(self.faces)
+        v, f = v.reshape(-1, 3), f.reshape(-1, 3).astype(np.int64)
+        double = v.dtype == np.float64
+        vfmt = "%.17g" if double else "%.9g"
+        if not double:
+            v = v.astype(np.float32)
+        vlines = [" ".join(vfmt % x for x in row) for row in v.tolist()]
+        if ft == "off":
+            head = ["OFF", f"{len(v)} {len(f)} 0"]
+            body = vlines + ["3 %d %d %d" % tuple(r) for r in f.tolist()]
+        elif ft == "ply":
+            kind = "double" if double else "float"
+            head = ["ply", "format ascii 1.0", f"element vertex {len(v)}", f"property {kind} x", f"property {kind} y",
+                    f"property {kind} z", f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+            body = vlines + ["3 %d %d %d" % tuple(r) for r in f.tolist()]
+        else:
+            head = []
+            body = ["v " + line for line in vlines] + ["f %d %d %d" % tuple(r) for r in (f + 1).tolist()]
+        with open(file_obj, "w") as fh:
+            fh.write("\n".join(head + body) + "\n")
+
+
 _tensor_version = operator.attrgetter("_version")
 
 
@@ -143,8 +182,11 @@ class Generator3D(object):
     def __init__(self, model, points_batch_size=100000, threshold=0.5, refinement_step=0, device=None,
                  resolution0=16, upsampling_steps=3, with_normals=False, padding=0.1, sample=False,
                  input_type=None, vol_info=None, vol_bound=None, simplify_nfaces=None, alpha=0.2,
-                 with_img=False, encode_t2d=False, decode_precision="f16x3", depth_origin=None):
+                 with_img=False, encode_t2d=False, decode_precision="f16x3", depth_origin=None, reference_returns=False):
         self.model = model.to(device)
+        # True: generate_obj_mesh_wnf returns (mesh, emd, cd) as the reference's does (generation.py:274-284) -- the metrics of
+        # the mesh against data['points.points_obj'], computed on the device (reference_metrics); False: the mesh alone
+        self.reference_returns = reference_returns
         # arithmetic of the dense lattice decode (eval_lattice): "f16x3" = split-f16 MFMA (the default: f32-level logit error,
         # ~1e-6 on the goldens, for hidden activations below 65504 -- guarded, see _range_guarded), "bf16x3" = split-bf16 MFMA
         # (f32's exponent range, ~1.6e-5), "f32" = exact-f32 MFMA, "f16f8" = f16 products + fp8 correction products (opt-in:
@@ -570,10 +612,42 @@ class Generator3D(object):
         v = (v - centroid.double()) / (2.0 * m.double())
         return Mesh(v, c_hand['mano_faces'])
 
-    @_range_guarded
     def generate_obj_mesh_wnf(self, data, c_img_all=None):
         """Encode -> dense decode -> marching cubes for one scene; ``data['inputs']`` is the
-        point cloud [1,T,3].  Returns Mesh(vertices [V,3] f32, faces [F,3] i32) on the device."""
+        point cloud [1,T,3].  Returns Mesh(vertices [V,3] f32, faces [F,3] i32) on the device -- or, with
+        ``reference_returns``, (mesh, emd, cd) as the reference does (see reference_metrics)."""
+        mesh = self._generate_obj_mesh(data, c_img_all)
+        if not self.reference_returns:
+            return mesh
+        emd, cd = self.reference_metrics(mesh, data)     # outside the range guard: the metrics are of the scene it kept
+        return mesh, emd, cd
+
+    def reference_metrics(self, mesh, data):
+        """(emd, cd) of the reference's generate_obj_mesh_wnf (generation.py:274-284): the mesh's vertices shuffled with numpy's
+        global generator (np.random.shuffle of their indices draws what the reference's in-place shuffle of the [V,3] array
+        draws), the first 2048 kept, then ``chamfer_distance(points_obj, vertices, use_kdtree=False).item()`` and
+        ``EarthMoverDistance(points_obj[0], vertices)`` -- both on the device (eval.chamfer_distance_device,
+        eval.earth_mover_distance_device).  ``data['points.points_obj']`` [1,T,3] is required.  An empty mesh gives
+        (nan, nan), where the reference fails inside scikit-image's marching cubes."""
+        import numpy as np
+        from ..eval import chamfer_distance_device, earth_mover_distance_device
+        points_obj = data.get('points.points_obj')
+        if points_obj is None:
+            raise VtError("Generator3D(reference_returns=True): data has no 'points.points_obj' to measure the mesh against")
+        V = int(mesh.vertices.shape[0])
+        if V == 0:
+            return float("nan"), float("nan")
+        order = np.arange(V)
+        np.random.shuffle(order)
+        verts = mesh.vertices.index_select(0, torch.from_numpy(order[:2048]).to(mesh.vertices.device)).float().contiguous()
+        target = points_obj.to(verts.device).float()
+        cd = chamfer_distance_device(target, verts.unsqueeze(0))
+        emd = earth_mover_distance_device(target[0].contiguous(), verts)
+        return emd, float(cd.item())
+
+    @_range_guarded
+    def _generate_obj_mesh(self, data, c_img_all=None):
+        """The mesh of generate_obj_mesh_wnf, under the half-precision decodes' range guard."""
         self._eval_mode()
         nx = self.resolution0 * 4                       # generation.py:120
         inputs = data.get('inputs').to(self.device)
