@@ -521,6 +521,30 @@ int vt_mc_emit(const float *vol, int n0, int n1, int n2, void *workspace,
                int rescale, float shift, float scale, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Multiresolution isosurface extraction (MISE): one refinement step on the device.                                          */
+/* Replaces: MultiGridExtractor (src/utils/mesh.py:7-84, with check_voxel_boundary, src/utils/voxels.py:222-257), which the   */
+/*   reference keeps but never calls.  Grids are x-major [n][n][n] f32 (marching cubes' layout), lattice ids g = (x n + y) n + z, */
+/*   coordinates box * linspace(-0.5, 0.5, n) computed as the decode kernels' lattice does.  n <= VT_MISE_MAX_N.                */
+/* vt_mise_lattice: ids[g] = g (ids may be NULL) and pts[g] = the coordinates of lattice point g, for all n^3 points.          */
+/* vt_mise_refine: from the coarse grid [nc]^3 to the fine grid [nf]^3, nf = 2 nc - 1.  active [(nc-1)^3] u8 (workspace, left  */
+/*   holding the classification): a coarse voxel is active when its 8 corners are not all on one side of `level`, the side     */
+/*   being marching cubes' own (double)v - level > 0 (the reference: v < threshold; they differ only where v equals the level). */
+/*   fine[(x,y,z)] = coarse[(x/2, y/2, z/2)]; fine point (2i,2j,2l) is known where coarse_known [nc^3] u8 says (NULL: every    */
+/*   coarse point known), the others are not.  An unknown fine point that is a corner of a fine voxel whose parent coarse voxel */
+/*   is active is appended to the query list (qids [capacity] i32, qpts                                                         */
+/*   [capacity][3] f32) in an order that varies from run to run.  *count (a device word, zeroed by the call) receives the      */
+/*   number of query points; only the first `capacity` are written -- a count above it asks for a larger list and another     */
+/*   call.  known [nf^3] u8 (the fine known mask before the query list is decoded) may be NULL.                                */
+/* vt_mise_scatter: fine[ids[i]] = vals[i] (and known[ids[i]] = 1 when known is not NULL) for i < m; ids outside [0, total)    */
+/*   are skipped.                                                                                                                */
+#define VT_MISE_MAX_N 513
+int vt_mise_lattice(int n, float box, int *ids, float *pts, void *stream);
+int vt_mise_refine(const float *coarse, const unsigned char *coarse_known, int nc, double level, float box, unsigned char *active, float *fine,
+                   unsigned char *known, int *qids, float *qpts, int64_t capacity, int *count, void *stream);
+int vt_mise_scatter(const int *ids, const float *vals, int64_t m, float *fine, int64_t total, unsigned char *known,
+                    void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* PointNet local-pool voxeliser.                                              */
 /* Replaces: normalize_3d_coordinate + coordinate2index (src/common.py:293-309, */
 /*   333-348; call site src/encoder/pointnet.py:151-152), torch_scatter          */

@@ -66,7 +66,8 @@ def get_generator(model, cfg, device, **kwargs):
                        refinement_step=g.get('refinement_step', 0), simplify_nfaces=g.get('simplify_nfaces'),
                        input_type=cfg['data']['input_type'], padding=cfg['data']['padding'],
                        with_img=cfg['model'].get('with_img', False), encode_t2d=cfg['model'].get('encoder_t2d', False),
-                       reference_returns=kwargs.get('reference_returns', g.get('reference_returns', False)))
+                       reference_returns=kwargs.get('reference_returns', g.get('reference_returns', False)),
+                       extraction=g.get('extraction', 'dense'))
 
 
 def get_trainer(model, optimizer, cfg, device, **kwargs):

@@ -172,7 +172,24 @@ def _reduce_or(word, group, device):
 
 
 class Generator3D(object):
-    """Constructor arguments as the reference (generation.py:42-52)."""
+    """Constructor arguments as the reference (generation.py:42-52), plus ``extraction``: how generate_obj_mesh_wnf samples the field.
+
+    ``"dense"`` (the default, the reference's behaviour): the nx^3 lattice, nx = resolution0 * 4, decoded whole, then marching cubes
+    at scikit-image's default level with the reference's ``-nx/2, (1+padding)/nx`` rescale; ``upsampling_steps`` is ignored, as the
+    reference ignores it.
+
+    ``"mise"``: multiresolution isosurface extraction (vtaco_amd/mise.py) from ``resolution0`` with ``upsampling_steps`` refinements,
+    n = resolution0 * 2^upsampling_steps + 1 points per axis (at most 513): the (r0+1)^3 lattice, then per level only the corners of
+    the voxels the surface crosses are decoded.  The level is the logit of ``threshold`` (``log(t) - log(1-t)`` in double: 0 at 0.5,
+    as ConvONet), and the vertices are rescaled by ``(n-1)/2, (1+padding)/(n-1)`` so that they lie in the frame the field was sampled
+    in.  Every level decodes through the POINT path -- ``decode_precision`` where that path has the arithmetic, ``"f16x3"`` for
+    ``"f16f8"`` (a lattice-only form) -- so a known entry is bit for bit the point-path decode of the same point of the dense n^3
+    lattice.  All three routes of generate_obj_mesh_wnf take it (visual: eager, not graph-captured; VTacOH and VTacO t2d: finger ids
+    assigned at the query points), under the same range guard.  Refused (VtError): the attention decoder (TransformerFusion couples
+    the points of a chunk: a sparse subset is not the dense field), a caller-supplied ``c_img_all`` (indexed by the dense lattice),
+    generate_obj_mesh_sharded and generate_mesh_graphed."""
+
+    EXTRACTIONS = ("dense", "mise")
 
     MAX_SCENE_GRAPHS = 4
     FUSED_CHUNKS_PER_CALL = 256          # attention_local: chunks of points_batch_size points evaluated per launch sequence (see _fused_chunks_per_call)
@@ -182,7 +199,14 @@ class Generator3D(object):
     def __init__(self, model, points_batch_size=100000, threshold=0.5, refinement_step=0, device=None,
                  resolution0=16, upsampling_steps=3, with_normals=False, padding=0.1, sample=False,
                  input_type=None, vol_info=None, vol_bound=None, simplify_nfaces=None, alpha=0.2,
-                 with_img=False, encode_t2d=False, decode_precision="f16x3", depth_origin=None, reference_returns=False):
+                 with_img=False, encode_t2d=False, decode_precision="f16x3", depth_origin=None, reference_returns=False,
+                 extraction="dense"):
+        if extraction not in self.EXTRACTIONS:
+            raise VtError(f"Generator3D: extraction must be one of {self.EXTRACTIONS} (got {extraction!r})")
+        if extraction == "mise" and hasattr(getattr(model, "decoder", None), "fuser"):
+            raise VtError("Generator3D(extraction='mise'): the attention decoder couples the points of a chunk (TransformerFusion), "
+                          "so the field at a sparse subset of the lattice is not the dense field; use extraction='dense'")
+        self.extraction = extraction
         self.model = model.to(device)
         # True: generate_obj_mesh_wnf returns (mesh, emd, cd) as the reference's does (generation.py:274-284) -- the metrics of
         # the mesh against data['points.points_obj'], computed on the device (reference_metrics); False: the mesh alone
@@ -412,7 +436,8 @@ class Generator3D(object):
         """Same result as ``generate_obj_mesh_wnf({'inputs': inputs})`` for the visual branch, with the
         ~110 launches of encode + decode + marching-cubes classification replayed as one hipGraph
         (launch-bound otherwise); only the data-dependent output sizing leaves the graph.  Safe across weight
-        updates and interleaved eager calls of other shapes (see ``_scene_graph``)."""
+        updates and interleaved eager calls of other shapes (see ``_scene_graph``).  Dense extraction only."""
+        self._refuse_mise("generate_mesh_graphed")
         self._eval_mode()
         nx = self.resolution0 * 4
         g = self._scene_graph(inputs.shape, nx)
@@ -428,8 +453,10 @@ class Generator3D(object):
         """``generate_obj_mesh_wnf`` with the lattice split over the ranks of a process group (one process per GPU):
         every rank encodes the scene (cheap, deterministic: no broadcast), decodes its slab of x-plane pairs with no
         data-path collective, one all_gather of the logit slabs (8.4 MB at 128^3, 67 MB at 256^3) rebuilds the value
-        grid, and every rank extracts the (identical) mesh.  Without an initialised group this is the single-GPU path."""
+        grid, and every rank extracts the (identical) mesh.  Without an initialised group this is the single-GPU path.
+        Dense extraction only."""
         from .. import dist as vdist
+        self._refuse_mise("generate_obj_mesh_sharded")
         self._eval_mode()
         nx = self.resolution0 * 4
         inputs = data.get('inputs').to(self.device)
@@ -649,6 +676,8 @@ class Generator3D(object):
     def _generate_obj_mesh(self, data, c_img_all=None):
         """The mesh of generate_obj_mesh_wnf, under the half-precision decodes' range guard."""
         self._eval_mode()
+        if self.extraction == "mise":
+            return self._generate_mise(data, c_img_all)
         nx = self.resolution0 * 4                       # generation.py:120
         inputs = data.get('inputs').to(self.device)
         if self.with_img and c_img_all is None:
@@ -699,8 +728,16 @@ class Generator3D(object):
         launch-bound kernels on a few CUs) and, in the VTacOH branch, the hand encoder (0.44 ms) -- so their graphs are replayed on
         three HIP streams at once and joined in front of the decode: 2.3 ms of encoders one after the other become the longest one.
         The setup's host side (contact clouds in numpy, the fingertips' frame change) runs under them."""
-        self._eval_mode()
         nx = self.resolution0 * 4
+        c, setup = self._tactile_encode(data)
+        with torch.no_grad():
+            values = self._eval_lattice_tactile(c, nx, setup)
+        return self.extract_mesh(values.reshape(nx, nx, nx))
+
+    def _tactile_encode(self, data):
+        """(c, setup) of a tactile scene: the shape encoder's output and the branch's finger features, anchors and rule, with the
+        encoders overlapped on the side streams (see _generate_tactile)."""
+        self._eval_mode()
         inputs = data.get('inputs').to(self.device)
         if inputs.shape[0] != 1:
             raise VtError(f"generate_obj_mesh_wnf: one scene at a time (got a batch of {inputs.shape[0]})")
@@ -717,9 +754,74 @@ class Generator3D(object):
         else:
             c = self._replay("encode_inputs", [inputs], self.model.encode_inputs)
             setup = self._tactile_setup(data)
-        with torch.no_grad():
-            values = self._eval_lattice_tactile(c, nx, setup)
-        return self.extract_mesh(values.reshape(nx, nx, nx))
+        return c, setup
+
+    # -- multiresolution isosurface extraction (extraction="mise") --------------------------------------------------------------
+    def _refuse_mise(self, what):
+        if self.extraction == "mise":
+            raise VtError(f"Generator3D.{what}: dense extraction only (this generator has extraction='mise'; use generate_obj_mesh_wnf)")
+
+    def mise_level(self):
+        """The iso level of extraction="mise": the logit of ``threshold``, log(t) - log(1-t) in double (0.0 at 0.5)."""
+        import math
+        t = float(self.threshold)
+        return math.log(t) - math.log(1.0 - t)
+
+    def _mise_precision(self):
+        """The point path's arithmetic for ``decode_precision``: "f16f8" is lattice-only, its points run as "f16x3"."""
+        return "f16x3" if self.decode_precision == "f16f8" else self.decode_precision
+
+    def mise_evaluator(self, c, setup=None):
+        """``evaluate(ids, pts) -> logits`` of the scene's decoder at arbitrary points for mise.extract: the point path in
+        ``_mise_precision()``; with a tactile ``setup`` every point first gets its finger id (vt_tactile_assign at the points) and
+        the decoder reads the finger's feature by id."""
+        dec = self.model.decoder
+        grid = dec._grid_of(c) if isinstance(c, dict) else c
+        prec = self._mise_precision()
+        if setup is None:
+            def evaluate(ids, pts):
+                p = pts.reshape(1, -1, 3)
+                if dec._wide:
+                    return dec._wide_fwd(grid, precision=prec, pts=p).reshape(-1)
+                return ops.decode_fwd(grid, dec._blob(precision=prec), pts=p, padding=dec.padding, precision=prec).reshape(-1)
+            return evaluate
+        dev = self.device
+        anchors, success = setup['anchors'].to(dev), setup['success'].to(dev)
+        count, feats = setup['count'].to(dev), setup['feats'].to(dev).float().contiguous()
+
+        def evaluate_tactile(ids, pts):
+            p = pts.reshape(1, -1, 3)
+            fid = ops.tactile_assign(anchors, success, setup['mode'], setup['radius'], pts=p, count=count)
+            if dec._wide:
+                return dec._wide_fwd(grid, precision=prec, pts=p, finger_ids=fid, finger_feats=feats).reshape(-1)
+            return ops.decode_fwd_ids(grid, dec._blob(img=True, precision=prec), fid, feats, pts=p, padding=dec.padding,
+                                      precision=prec).reshape(-1)
+        return evaluate_tactile
+
+    def _generate_mise(self, data, c_img_all=None):
+        """generate_obj_mesh_wnf with extraction="mise": the route's encoders as the dense route runs them, then mise.extract
+        instead of the lattice decode, then marching cubes at the threshold's logit in the sampled frame.  The points each level
+        decoded are left in ``self.mise_points_per_level``."""
+        from .. import mise
+        if c_img_all is not None:
+            raise VtError("Generator3D(extraction='mise'): c_img_all is indexed by the dense nx^3 lattice; pass the tactile inputs "
+                          "instead (the route assigns finger ids at the query points)")
+        inputs = data.get('inputs').to(self.device)
+        if inputs.shape[0] != 1:
+            raise VtError(f"generate_obj_mesh_wnf: one scene at a time (got a batch of {inputs.shape[0]})")
+        if self.with_img:
+            c, setup = self._tactile_encode(data)
+        else:
+            with torch.no_grad():
+                c = self.model.encode_inputs(inputs)
+            setup = None
+        box, level = 1 + self.padding, self.mise_level()
+        values, _, per_level = mise.extract(self.mise_evaluator(c, setup), self.resolution0, self.upsampling_steps, level, box,
+                                            self.device)
+        self.mise_points_per_level = per_level
+        n = values.shape[0]
+        verts, faces, _ = ops.marching_cubes(values, level, rescale=((n - 1) / 2, box / (n - 1)))
+        return Mesh(verts, faces)
 
     def _setup_vtaco_t2d(self, data, sides=None):
         """The VTacO branch of generate_obj_mesh_wnf (generation.py:202-257): per finger whose touch succeeded, the contact cloud
