@@ -123,11 +123,14 @@ __host__ __device__ inline long long pu_ws_offset(const PuDims &d, int i) {
     return off;
 }
 
-// the K split inside a workgroup: waves per output tile (each takes Cin / KS input channels, a whole number of 8-channel chunks)
+// the K split inside a workgroup: waves per output tile (each takes Cin / KS input channels, a whole number of 8-channel chunks:
+// Cin is a multiple of 32, so 4 waves always divide it; 8 only where Cin is a multiple of 64 -- Cin 96 over 8 waves would drop 32)
 inline int pu_waves(int Cin, int ntaps) {
     const int target = ntaps == 9 ? Cin / 8 : Cin / 32;              // 8 channels x 9 taps = 36 MFMAs per wave
-    return target >= 8 ? 8 : 4;           // (16 waves leave 128 registers per lane: the loader's loads in flight do not fit)
+    return target >= 8 && Cin % (8 * PU_CH) == 0 ? 8 : 4;   // (16 waves leave 128 registers per lane: the loader's loads in flight do not fit)
 }
+// the phase kernel walks Cin / (KS * 8) chunks per wave: a remainder would be dropped silently
+inline bool pu_split_ok(int Cin, int KS) { return Cin > 0 && Cin % (KS * PU_CH) == 0; }
 
 struct PuArgs {
     PuDims d;
@@ -827,6 +830,10 @@ int vt_plane_unet_fwd(const float *x, int n_img, int H, int W, const vt_plane_un
         return vt_fail(VT_ERR_WORKSPACE, "vt_plane_unet_fwd: workspace too small");
     PuArgs a;
     a.d = d; a.x = x; a.blob = blob; a.out = out; a.ws = reinterpret_cast<float *>(workspace);
+    for (int i = 0; i < pu_n_phases(d); ++i) {
+        const PuPhase p = pu_phase(a, i);
+        if (!pu_split_ok(p.Cin, p.KS)) return vt_fail(VT_ERR_UNSUPPORTED, "vt_plane_unet_fwd: a phase's K split would drop input channels");
+    }
     for (int i = 0; i < pu_n_phases(d); ++i) pu_launch(pu_phase(a, i), (hipStream_t)stream);
     return vt_check(hipGetLastError(), "vt_plane_unet_fwd");
 }
@@ -850,6 +857,10 @@ int vt_plane_unet_bwd(const float *x, int n_img, int H, int W, const vt_plane_un
     a.f.ws = const_cast<float *>(reinterpret_cast<const float *>(fwd_workspace));
     a.dout = dout; a.bws = reinterpret_cast<float *>(workspace); a.dx = dx;
     const int n = pu_n_phases(d), D = d.depth;
+    for (int j = 0; j < n; ++j) {
+        const PuPhase p = pu_phase_bwd(a, j);
+        if (!pu_split_ok(p.Cin, p.KS)) return vt_fail(VT_ERR_UNSUPPORTED, "vt_plane_unet_bwd: a phase's K split would drop input channels");
+    }
     PuFinAll fin{};
     fin.n = n;
     PuWg wg[PU_MAX_PHASES];
