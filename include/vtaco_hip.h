@@ -545,6 +545,24 @@ int vt_mise_scatter(const int *ids, const float *vals, int64_t m, float *fine, i
                     void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Touch session: one touch merged into the id lattice an object keeps across touches.                                          */
+/* Replaces: the carried-over c_img_all of Inferencer.inference_img / inference_img_t2d (src/conv_onet/inferencing.py:155-170,     */
+/*   274-313): created at the first touch, every later touch writes its fingers' features where its fingers are.                 */
+/* ids [nx^3] u8 holds per lattice point the ROW of the session's feature table, 255 = no row.  vt_touch_merge evaluates         */
+/*   vt_tactile_assign's rule (same arguments, same arithmetic, lattice mode, first = 0) at every lattice point; where it names   */
+/*   finger f, ids[g] = row_base + f and g is appended to the list (changed_ids [capacity] i32, changed_pts [capacity][3] f32: the */
+/*   lattice's coordinates); every other ids[g] is left alone.  The list is in ASCENDING lattice order on every run.              */
+/*   *n_changed (a device word) receives its length; only the first `capacity` entries are written -- a length above it asks for  */
+/*   a larger list (the ids are merged either way, so a second call with the same arguments lists the same points).               */
+/*   Only the part of the lattice the successful fingers' anchors (grown by the radius) can reach is visited.                     */
+/*   row_base + F > 254 is VT_ERR_UNSUPPORTED, before any launch.  workspace: vt_touch_workspace_bytes(nx) bytes.                  */
+/*   The decoded logits of the list go into the value lattice with vt_mise_scatter(changed_ids, logits, m, values, nx^3, NULL).   */
+size_t vt_touch_workspace_bytes(int nx);
+int vt_touch_merge(const float *anchors, const int *count, const unsigned char *success, int F, int K, int mode, double radius,
+                   int nx, float box, int row_base, unsigned char *ids, int *changed_ids, float *changed_pts, int64_t capacity,
+                   int *n_changed, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* PointNet local-pool voxeliser.                                              */
 /* Replaces: normalize_3d_coordinate + coordinate2index (src/common.py:293-309, */
 /*   333-348; call site src/encoder/pointnet.py:151-152), torch_scatter          */

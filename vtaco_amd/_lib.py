@@ -176,6 +176,8 @@ SIGNATURES = {
     "vt_mise_lattice": (_I, [_I, _F, _VP, _VP, _VP]),
     "vt_mise_refine": (_I, [_VP, _VP, _I, _D, _F, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "vt_mise_scatter": (_I, [_VP, _VP, _I64, _VP, _I64, _VP, _VP]),
+    "vt_touch_workspace_bytes": (_SZ, [_I]),
+    "vt_touch_merge": (_I, [_VP, _VP, _VP, _I, _I, _I, _D, _I, _F, _I, _VP, _VP, _VP, _I64, _VP, _VP, _SZ, _VP]),
     "vt_mc_read_counts_begin": (_I, [_VP, _VP, ctypes.POINTER(_I)]),
     "vt_mc_read_counts_end": (_I, [_I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_D)]),
     "vt_mc_emit": (_I, [_VP, _I, _I, _I, _VP, _VP, _I, _VP, _I, _I, _F, _F, _VP]),

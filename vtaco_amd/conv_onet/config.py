@@ -82,6 +82,19 @@ def get_trainer(model, optimizer, cfg, device, **kwargs):
                    depth_origin=kwargs.get('depth_origin'))
 
 
+def get_inferencer(model, optimizer, generator, cfg, device, **kwargs):
+    """reference conv_onet/config.py:183-213: the multi-touch Inferencer from the same config keys; ``incremental=False`` (keyword)
+    for the whole-lattice decode on every touch."""
+    import os
+    from .inferencing import Inferencer
+    m = cfg['model']
+    return Inferencer(model, optimizer, generator, device=device, input_type=cfg['data']['input_type'],
+                      vis_dir=os.path.join(cfg['training']['out_dir'], 'vis'), threshold=cfg['test']['threshold'],
+                      eval_sample=cfg['training']['eval_sample'], num_sample=cfg['data']['num_sample'],
+                      with_img=m['with_img'], with_contact=m['with_contact'], train_tactile=m['train_tactile'],
+                      encode_t2d=bool(m['encoder_t2d']), incremental=kwargs.get('incremental', True))
+
+
 def get_data_fields(mode, cfg):
     """Method-specific fields of a sample (reference conv_onet/config.py:272-318): the query points
     with occupancies ('points'), and for val / test the IoU points ('points_iou')."""

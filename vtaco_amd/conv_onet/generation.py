@@ -608,15 +608,20 @@ class Generator3D(object):
         -> the reference's R_from_PYR convention, common.py:591-604), plus the wrist position, normalised by
         the object's ``inputs.pc_ply`` cloud (norm_pc_1, common.py:606-612).  Returns Mesh(vertices [778,3]
         f64, faces [1538,3] i64) on the device (the reference wraps the same arrays in a trimesh.Trimesh)."""
-        import numpy as np
-        from scipy.spatial.transform import Rotation
         self._eval_mode()
         inputs = data.get('inputs').to(self.device)
         pc_ply = data.get('inputs.pc_ply').to(self.device)
         if inputs.shape[0] != 1:
             raise VtError(f"generate_hand_mesh: one scene at a time (got a batch of {inputs.shape[0]})")
         c_hand = self._replay("encode_hand_inputs", [inputs], self.model.encode_hand_inputs)   # ~70 launches as one graph
-        if 'mano_verts' not in c_hand:
+        return self._hand_mesh_of(c_hand, pc_ply)
+
+    def _hand_mesh_of(self, c_hand, pc_ply):
+        """generate_hand_mesh's arithmetic on a hand encoder output that is already there (the touch session's VTacOH route runs
+        the hand encoder once per touch for the fingertips and the mesh)."""
+        import numpy as np
+        from scipy.spatial.transform import Rotation
+        if not isinstance(c_hand, dict) or 'mano_verts' not in c_hand:
             raise VtError("generate_hand_mesh: the hand encoder has no MANO layer (out_dim <= 30 regresses digit poses only)")
         param = c_hand['mano_param'][0].double().cpu().numpy()
 
@@ -890,5 +895,6 @@ class Generator3D(object):
                                               data.get('points.wrist').cpu().numpy(), data.get('inputs.pc_ply').float().cpu().numpy())
             anchors = torch.from_numpy(tips[0]).float().unsqueeze(1)                               # [5,1,3]
             return {'feats': c_img[0], 'anchors': anchors, 'success': data.get('inputs.touch_success')[0].to(torch.uint8),
-                    'mode': 'nearest', 'radius': 0.05, 'count': torch.ones(5, dtype=torch.int32)}
+                    'mode': 'nearest', 'radius': 0.05, 'count': torch.ones(5, dtype=torch.int32),
+                    'c_hand': c_hand}                               # (the graph's static output: valid until the next hand replay)
         return host_part if sides else host_part()
