@@ -1006,6 +1006,58 @@ int vt_plane_unet_bwd(const float *x, int n_img, int H, int W, const vt_plane_un
                       const vt_plane_unet_grads *grads_host, float *dx, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Tactile feature encoder, eval mode (resnet2d.hip).  Replaces                  */
+/*   ResNet.forward with BasicBlocks (src/layers.py:54-207: conv1 7x7/2, bn1,     */
+/*   relu, maxpool 3x3/2, layer1..4, avgpool, flatten, linear, fc :176-190), as   */
+/*   ConvolutionalOccupancyNetwork.encode_img_inputs calls it on the five tactile  */
+/*   images of a scene (src/conv_onet/models/__init__.py:115-136), with the        */
+/*   BatchNorm layers in eval mode (running statistics):                          */
+/*   x [n_img][3][H][W] (NCHW) -> out [n_img][num_classes].                        */
+/* vt_resnet_pack folds every BatchNorm into the conv before it (f64) and writes   */
+/*   the folded weights in fragment order (blob of vt_resnet_blob_bytes; repack    */
+/*   after every change of a weight OR a running statistic).  vt_resnet_fwd is     */
+/*   2 + 2 * (number of blocks) launches: the stem with the max-pool in its        */
+/*   epilogue, one launch per 3x3 conv (bias, residual and ReLU in the epilogue;   */
+/*   a stage's 1x1 stride-2 projection rides in its first conv's launch), one      */
+/*   tail (average pool, linear, fc).  Exact-f32 matrix core throughout; every     */
+/*   sum in a fixed order that does not depend on n_img: bit-reproducible, and an  */
+/*   image's features are the same bits in any batch.                             */
+/* Covered (vt_resnet_supported): blocks_num entries 1..VT_RESNET_MAX_BLOCKS,      */
+/*   num_classes 1..65536, 1 <= n_img <= 1024, 1 <= H, W <= 2048 (any values, odd  */
+/*   included), every tensor below 2^31 elements.  Unsupported: the size queries   */
+/*   return 0.  Workspace: four buffers of max over the stages s = 0..3 of         */
+/*   n_img * Hs * Ws * (64 << s) floats, Hs = ceil(H / 2^(s+2)), Ws alike.         */
+/* ------------------------------------------------------------------------- */
+#define VT_RESNET_MAX_BLOCKS 36
+typedef struct vt_resnet_bn {          /* nn.BatchNorm2d: weight, bias, running_mean, running_var [C]; eps */
+    const float *weight, *bias, *running_mean, *running_var;
+    double eps;
+} vt_resnet_bn;
+typedef struct vt_resnet_block {       /* layer{s}.{b}: conv1 [Cout][Cin][3][3], conv2 [Cout][Cout][3][3]     */
+    const float *conv1_w;
+    vt_resnet_bn bn1;
+    const float *conv2_w;
+    vt_resnet_bn bn2;
+    const float *down_w;               /* downsample.0.weight [Cout][Cin][1][1] (first block of layer2..4), else NULL */
+    vt_resnet_bn down_bn;              /* downsample.1 */
+} vt_resnet_block;
+typedef struct vt_resnet_params {
+    int32_t blocks_num[4];
+    int32_t num_classes;
+    const float *conv1_w;              /* conv1.weight [64][3][7][7] */
+    vt_resnet_bn bn1;
+    vt_resnet_block block[4][VT_RESNET_MAX_BLOCKS];
+    const float *linear_w, *linear_b;  /* linear [100][512], [100] */
+    const float *fc_w, *fc_b;          /* fc [num_classes][100], [num_classes] */
+} vt_resnet_params;
+int vt_resnet_supported(const int32_t *blocks_num, int num_classes, int n_img, int H, int W);
+size_t vt_resnet_blob_bytes(const int32_t *blocks_num, int num_classes);
+size_t vt_resnet_workspace_bytes(const int32_t *blocks_num, int num_classes, int n_img, int H, int W);
+int vt_resnet_pack(const vt_resnet_params *params_host, float *blob, size_t blob_bytes, void *stream);
+int vt_resnet_fwd(const float *x, int n_img, int H, int W, const vt_resnet_params *dims_host, const float *blob,
+                  void *workspace, size_t workspace_bytes, float *out, void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* PointNet per-point MLP (inference).  Replaces the nn.Linear / ResnetBlockFC   */
 /* calls of LocalPoolPointnet.forward (src/encoder/pointnet.py:154-162;           */
 /* src/layers.py:8-50): rows are points, weights in nn.Linear layout [out][in].   */

@@ -94,6 +94,28 @@ class PlaneUnetGrads(ctypes.Structure):
                 ("final_w", ctypes.c_void_p), ("final_b", ctypes.c_void_p)]
 
 
+VT_RESNET_MAX_BLOCKS = 36
+
+
+class ResnetBn(ctypes.Structure):
+    """Mirror of ``vt_resnet_bn``."""
+    _fields_ = [("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("running_mean", ctypes.c_void_p),
+                ("running_var", ctypes.c_void_p), ("eps", ctypes.c_double)]
+
+
+class ResnetBlock(ctypes.Structure):
+    """Mirror of ``vt_resnet_block``."""
+    _fields_ = [("conv1_w", ctypes.c_void_p), ("bn1", ResnetBn), ("conv2_w", ctypes.c_void_p), ("bn2", ResnetBn),
+                ("down_w", ctypes.c_void_p), ("down_bn", ResnetBn)]
+
+
+class ResnetParams(ctypes.Structure):
+    """Mirror of ``vt_resnet_params``."""
+    _fields_ = [("blocks_num", ctypes.c_int32 * 4), ("num_classes", ctypes.c_int32), ("conv1_w", ctypes.c_void_p), ("bn1", ResnetBn),
+                ("block", (ResnetBlock * VT_RESNET_MAX_BLOCKS) * 4),
+                ("linear_w", ctypes.c_void_p), ("linear_b", ctypes.c_void_p), ("fc_w", ctypes.c_void_p), ("fc_b", ctypes.c_void_p)]
+
+
 # name -> (restype, argtypes); kept in step with include/vtaco_hip.h (tests/test_abi.py
 # parses the header and checks that every declared symbol is exported and listed here)
 _VP, _I, _I64, _F, _D, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
@@ -215,6 +237,11 @@ SIGNATURES = {
     "vt_plane_unet_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
     "vt_plane_unet_pack": (_I, [ctypes.POINTER(PlaneUnetParams), _VP, _SZ, _VP]),
     "vt_plane_unet_fwd": (_I, [_VP, _I, _I, _I, ctypes.POINTER(PlaneUnetParams), _VP, _VP, _SZ, _VP, _VP]),
+    "vt_resnet_supported": (_I, [ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I]),
+    "vt_resnet_blob_bytes": (_SZ, [ctypes.POINTER(ctypes.c_int32), _I]),
+    "vt_resnet_workspace_bytes": (_SZ, [ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I]),
+    "vt_resnet_pack": (_I, [ctypes.POINTER(ResnetParams), _VP, _SZ, _VP]),
+    "vt_resnet_fwd": (_I, [_VP, _I, _I, _I, ctypes.POINTER(ResnetParams), _VP, _VP, _SZ, _VP, _VP]),
     "vt_plane_unet_bwd_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
     "vt_plane_unet_bwd": (_I, [_VP, _I, _I, _I, ctypes.POINTER(PlaneUnetParams), _VP, _VP, _VP, _VP, _SZ, ctypes.POINTER(PlaneUnetGrads), _VP, _VP]),
     "vt_mano_pack": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),

@@ -8,9 +8,21 @@ tiny per-point MLP (SURVEY.md K4, 0.16 GFLOP/scene, stays host PyTorch).
 """
 from __future__ import annotations
 
+import os
+
 import torch
 from torch import nn
 from torch.nn import functional as F
+
+from . import ops
+
+# the eval-mode forward of TactileResNet: "hip" = vt_resnet_fwd (csrc/resnet2d.hip), "host" = the nn modules (MIOpen)
+# (read at every call, so a tool can time both paths in one process)
+def _tactile_resnet_mode():
+    mode = os.environ.get("VTACO_TACTILE_RESNET", "hip")
+    if mode not in ("hip", "host"):
+        raise ValueError(f"VTACO_TACTILE_RESNET must be 'hip' or 'host' (got {mode!r})")
+    return mode
 
 
 class _TallLinear(torch.autograd.Function):
@@ -197,7 +209,9 @@ class TactileResNet(nn.Module):
     """Tactile feature encoder of the shipped VTacO / VTacOH configs (``encoder_img: Resnet18``; reference ``ResNet`` with
     BasicBlocks, src/layers.py:127-195): 7x7/2 stem, 3x3/2 max-pool, four stages of residual pairs (64, 128, 256, 512; stride 2
     from the second), global average pool, Linear(512, 100), Linear(100, num_classes) -- no activation between the two.
-    Host PyTorch-ROCm (MIOpen), like the tactile depth U-Net: five 320x240 images per scene."""
+    Five 320x240 images per scene.  In eval mode without autograd on a HIP f32 input the forward is ``vt_resnet_fwd``
+    (csrc/resnet2d.hip: BatchNorm folded into the convs, 18 launches for Resnet18, bit-reproducible); train mode, anything under
+    autograd and ``VTACO_TACTILE_RESNET=host`` run the nn modules (``forward_modules``: host PyTorch-ROCm / MIOpen)."""
 
     def __init__(self, blocks_num=(2, 2, 2, 2), num_classes=32):
         super().__init__()
@@ -225,7 +239,38 @@ class TactileResNet(nn.Module):
         blocks += [_ResidualPair(channel, channel) for _ in range(1, count)]
         return nn.Sequential(*blocks)
 
+    def hip_supported(self, x):
+        """Eval mode, no autograd through the call, a HIP f32 image batch, a shape vt_resnet_supported covers."""
+        if self.training or _tactile_resnet_mode() != "hip" or not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False
+        return x.shape[1] == 3 and x.shape[0] > 0 and ops.resnet_supported(self, x.shape[0], x.shape[2], x.shape[3])
+
+    def _blob_stamp(self):
+        """(storage, version) of every parameter AND buffer: load_state_dict, an optimiser step and a train-mode forward (running
+        statistics) all change it."""
+        return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+
+    def _blob(self):
+        """The packed weights (BatchNorm folded in), repacked when the stamp moved.  Generator3D runs every stage eagerly before it
+        captures it, so the packing launches never fall inside a stream capture."""
+        stamp = self._blob_stamp()
+        hit = self.__dict__.get("_blob_cache")
+        if hit is None or hit[0] != stamp:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("TactileResNet: weights changed since the last eager call; run one eval forward outside stream capture")
+            hit = (stamp, ops.resnet_pack(self))
+            self.__dict__["_blob_cache"] = hit
+        return hit[1]
+
     def forward(self, x, scenes=1):
+        if self.hip_supported(x):
+                return ops.resnet_fwd(x, self, self._blob())
+        return self.forward_modules(x, scenes)
+
+    def forward_modules(self, x, scenes=1):
+        """The nn modules one by one (host PyTorch-ROCm / MIOpen): train mode, autograd, shapes the HIP path does not cover."""
         x = self.maxpool(F.relu(_bn_scenes(self.bn1, self.conv1(x), scenes)))
         for stage in (self.layer1, self.layer2, self.layer3, self.layer4):
             for block in stage:

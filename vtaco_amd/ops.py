@@ -2107,6 +2107,135 @@ def plane_unet_fwd(x, net, blob, ws=None):
     return out
 
 
+# ---- the tactile feature encoder in eval mode (resnet2d.hip) -----------------------------------------------------------------------
+
+def resnet_fold_bn(weight, bn_weight, bn_bias, running_mean, running_var, eps):
+    """Eval-mode ``bn(conv(x))`` as one conv: (folded weight, bias) in float64 -- ``w * gamma / sqrt(var + eps)`` per output channel and
+    ``beta - mean * gamma / sqrt(var + eps)``.  vt_resnet_pack computes exactly this (f64) per fragment slot before it rounds to f32."""
+    s = bn_weight.detach().double() / torch.sqrt(running_var.detach().double() + float(eps))
+    w = weight.detach().double() * s.view(-1, *([1] * (weight.dim() - 1)))
+    return w, bn_bias.detach().double() - running_mean.detach().double() * s
+
+
+def _resnet_blocks(net):
+    arr = (ctypes.c_int32 * 4)(*(len(stage) for stage in (net.layer1, net.layer2, net.layer3, net.layer4)))
+    return arr, int(net.fc.out_features)
+
+
+def resnet_workspace_floats(blocks_num, n_img, H, W):
+    """The documented size of vt_resnet_fwd's workspace: four buffers of the largest stage's activations [n_img][Hs][Ws][64 << s],
+    Hs = ceil(H / 2^(s + 2))."""
+    up = lambda v: (v - 1) // 2 + 1
+    h, w, most = up(up(H)), up(up(W)), 0
+    for s in range(4):
+        most = max(most, n_img * h * w * (64 << s))
+        h, w = up(h), up(w)
+    return 4 * most
+
+
+def resnet_supported(net, n_img, H, W):
+    blocks, classes = _resnet_blocks(net)
+    if max(blocks) > _lib.VT_RESNET_MAX_BLOCKS or net.linear.in_features != 512 or net.linear.out_features != 100:
+        return False
+    return bool(_lib.load().vt_resnet_supported(blocks, classes, int(n_img), int(H), int(W)))
+
+
+def resnet_params(net):
+    """(ResnetParams, tensors it points to) of a ``layers.TactileResNet``: every conv weight, every BatchNorm's weight, bias, running
+    statistics and eps, linear and fc, in the state_dict's own layouts."""
+    prm = _lib.ResnetParams()
+    blocks, classes = _resnet_blocks(net)
+    for s in range(4):
+        prm.blocks_num[s] = blocks[s]
+    prm.num_classes = classes
+    keep = []
+
+    def ptr(t, name):
+        t = _c(t)
+        keep.append(t)
+        return dev_ptr(t, name).value
+
+    def bn(dst, m, name):
+        if m.weight is None or m.running_mean is None:
+            raise VtError(f"resnet_pack: {name} has no affine parameters or no running statistics")
+        dst.weight, dst.bias = ptr(m.weight, name + ".weight"), ptr(m.bias, name + ".bias")
+        dst.running_mean, dst.running_var = ptr(m.running_mean, name + ".running_mean"), ptr(m.running_var, name + ".running_var")
+        dst.eps = float(m.eps)
+    prm.conv1_w = ptr(net.conv1.weight, "conv1.weight")
+    bn(prm.bn1, net.bn1, "bn1")
+    for s, stage in enumerate((net.layer1, net.layer2, net.layer3, net.layer4)):
+        for b, blk in enumerate(stage):
+            k, name = prm.block[s][b], f"layer{s + 1}.{b}"
+            k.conv1_w, k.conv2_w = ptr(blk.conv1.weight, name + ".conv1.weight"), ptr(blk.conv2.weight, name + ".conv2.weight")
+            bn(k.bn1, blk.bn1, name + ".bn1")
+            bn(k.bn2, blk.bn2, name + ".bn2")
+            if (blk.downsample is not None) != (b == 0 and s > 0):
+                raise VtError(f"resnet_pack: {name}: a projection where the BasicBlock net has none (or none where it has one)")
+            if blk.downsample is not None:
+                k.down_w = ptr(blk.downsample[0].weight, name + ".downsample.0.weight")
+                bn(k.down_bn, blk.downsample[1], name + ".downsample.1")
+    prm.linear_w, prm.linear_b = ptr(net.linear.weight, "linear.weight"), ptr(net.linear.bias, "linear.bias")
+    prm.fc_w, prm.fc_b = ptr(net.fc.weight, "fc.weight"), ptr(net.fc.bias, "fc.bias")
+    return prm, keep
+
+
+def resnet_pack(net):
+    """The net's convs with their BatchNorms folded in, in fragment order, + linear and fc: the blob vt_resnet_fwd reads (vt_resnet_pack)."""
+    lib = _lib.load()
+    blocks, classes = _resnet_blocks(net)
+    n = lib.vt_resnet_blob_bytes(blocks, classes) if max(blocks) <= _lib.VT_RESNET_MAX_BLOCKS else 0
+    if n == 0:
+        raise VtError("tactile ResNet not built for this net (vt_resnet_supported)")
+    prm, keep = resnet_params(net)
+    blob = torch.empty(n // 4, dtype=torch.float32, device=keep[0].device)
+    check(lib.vt_resnet_pack(ctypes.byref(prm), dev_ptr(blob, "blob"), n, stream_ptr()), "vt_resnet_pack")
+    return blob
+
+
+_resnet_ws = {}        # (device, stream, blocks, images, H, W) -> workspace; at most _RESNET_WS_MAX entries, the oldest leaves first
+_RESNET_WS_MAX = 8
+
+
+def resnet_workspace(net, n_img, H, W):
+    """Workspace of vt_resnet_fwd, one per (device, STREAM, shape): two encoders replayed side by side on two streams must not share
+    their activations.  A captured graph keeps its workspace alive itself (keep_for_graph), so eviction is safe."""
+    lib = _lib.load()
+    dev = torch.cuda.current_device()
+    blocks, classes = _resnet_blocks(net)
+    key = (dev, torch.cuda.current_stream().cuda_stream, tuple(blocks), classes, int(n_img), int(H), int(W))
+    ws = _resnet_ws.get(key)
+    if ws is None:
+        n = lib.vt_resnet_workspace_bytes(blocks, classes, int(n_img), int(H), int(W))
+        if n == 0:
+            raise VtError("tactile ResNet shape not built (vt_resnet_supported)")
+        ws = torch.empty(n, dtype=torch.uint8, device=torch.device("cuda", dev))
+        while len(_resnet_ws) >= _RESNET_WS_MAX:
+            _resnet_ws.pop(next(iter(_resnet_ws)))
+        _resnet_ws[key] = ws
+    keep_for_graph(ws)
+    return ws
+
+
+def resnet_fwd(x, net, blob, ws=None):
+    """TactileResNet.forward in eval mode on the HIP kernels: x [n_img, 3, H, W] -> [n_img, num_classes] (vt_resnet_fwd)."""
+    x = _c(x)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise VtError(f"resnet_fwd: input must be [n_img, 3, H, W] (got {tuple(x.shape)})")
+    n_img, _, H, W = x.shape
+    if ws is None:
+        ws = resnet_workspace(net, n_img, H, W)
+    prm = _lib.ResnetParams()
+    blocks, classes = _resnet_blocks(net)
+    for s in range(4):
+        prm.blocks_num[s] = blocks[s]
+    prm.num_classes = classes
+    out = torch.empty((n_img, classes), dtype=torch.float32, device=x.device)
+    keep_for_graph(blob, x)
+    check(_lib.load().vt_resnet_fwd(dev_ptr(x, "x"), n_img, H, W, ctypes.byref(prm), dev_ptr(blob, "blob"),
+                                    ctypes.c_void_p(ws.data_ptr()), ws.numel(), dev_ptr(out, "out"), stream_ptr()), "vt_resnet_fwd")
+    return out
+
+
 def plane_unet_bwd(x, net, blob, fwd_ws, dout):
     """Backward of plane_unet_fwd (vt_plane_unet_bwd): (dx, {parameter name: gradient}) from dout, the input, the packed weights and the
     workspace the forward filled.  Gradients are written, not accumulated."""
