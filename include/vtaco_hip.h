@@ -1058,6 +1058,49 @@ int vt_resnet_fwd(const float *x, int n_img, int H, int W, const vt_resnet_param
                   void *workspace, size_t workspace_bytes, float *out, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Tactile depth estimator, eval mode (unet2d.hip).  Replaces UNet.forward        */
+/*   (src/layers.py:322-450; up_mode 'transpose', merge_mode 'concat': `depth`     */
+/*   DownConvs, depth - 1 UpConvs, conv_final, sigmoid) as                         */
+/*   ConvolutionalOccupancyNetwork.encode_img_inputs calls it on the five tactile  */
+/*   images of a scene, with the BatchNorm layers in eval mode:                    */
+/*   x [n_img][in_channels][H][W] (NCHW) -> out [n_img][num_classes][H][W].        */
+/* vt_tactile_unet_pack folds each block's ONE BatchNorm into both of its convs     */
+/*   (f64) and writes the folded weights in fragment order (blob of                */
+/*   vt_tactile_unet_blob_bytes; repack after every change of a weight OR a         */
+/*   running statistic).  vt_tactile_unet_fwd is 2 depth + 3 (depth - 1) launches   */
+/*   (12 at depth 3): one per 3x3 conv with bias + ReLU in its epilogue -- a down   */
+/*   block's second conv also writes the 2x2 max-pool, an up block's first conv     */
+/*   reads the up-conv's result and the skip as two sources (no concat), the last   */
+/*   conv ends in conv_final + sigmoid -- and one per transposed conv (its four     */
+/*   output parities as four 1x1 GEMMs).  Exact-f32 matrix core, every sum in a     */
+/*   fixed order that does not depend on n_img: bit-reproducible, and an image's    */
+/*   result is the same bits in any batch.                                          */
+/* Covered (vt_tactile_unet_supported): depth 1..5, start_filts 8..64 (multiple of  */
+/*   8), in_channels 1..4, num_classes 1..4, 1 <= n_img <= 1024, H and W multiples  */
+/*   of 2^(depth-1) up to 2048, n_img * H * W * start_filts < 2^31.  Unsupported:   */
+/*   the size queries return 0.                                                     */
+/* up_* entries are indexed by the level the block produces: up_*[i] is             */
+/*   up_convs[depth - 2 - i] (start_filts << i output channels), i = 0..depth-2.    */
+/* ------------------------------------------------------------------------- */
+#define VT_TACTILE_UNET_MAX_DEPTH 5
+#define VT_TACTILE_UNET_MAX_CLASSES 4
+typedef struct vt_tactile_unet_params {
+    int32_t depth, start_filts, in_channels, num_classes;
+    const float *down_w[VT_TACTILE_UNET_MAX_DEPTH][2], *down_b[VT_TACTILE_UNET_MAX_DEPTH][2];   /* down_convs[i].conv1 / conv2 */
+    vt_resnet_bn down_bn[VT_TACTILE_UNET_MAX_DEPTH];                                             /* down_convs[i].bn (behind both convs) */
+    const float *up_tw[VT_TACTILE_UNET_MAX_DEPTH], *up_tb[VT_TACTILE_UNET_MAX_DEPTH];           /* upconv.weight [2C][C][2][2], bias [C] */
+    const float *up_w[VT_TACTILE_UNET_MAX_DEPTH][2], *up_b[VT_TACTILE_UNET_MAX_DEPTH][2];       /* conv1 [C][2C][3][3], conv2 [C][C][3][3] */
+    vt_resnet_bn up_bn[VT_TACTILE_UNET_MAX_DEPTH];
+    const float *final_w, *final_b;                                                              /* conv_final [num_classes][start_filts][1][1] */
+} vt_tactile_unet_params;
+int vt_tactile_unet_supported(int depth, int start_filts, int in_channels, int num_classes, int n_img, int H, int W);
+size_t vt_tactile_unet_blob_bytes(int depth, int start_filts, int in_channels, int num_classes);
+size_t vt_tactile_unet_workspace_bytes(int depth, int start_filts, int in_channels, int num_classes, int n_img, int H, int W);
+int vt_tactile_unet_pack(const vt_tactile_unet_params *params_host, float *blob, size_t blob_bytes, void *stream);
+int vt_tactile_unet_fwd(const float *x, int n_img, int H, int W, const vt_tactile_unet_params *dims_host, const float *blob,
+                        void *workspace, size_t workspace_bytes, float *out, void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* PointNet per-point MLP (inference).  Replaces the nn.Linear / ResnetBlockFC   */
 /* calls of LocalPoolPointnet.forward (src/encoder/pointnet.py:154-162;           */
 /* src/layers.py:8-50): rows are points, weights in nn.Linear layout [out][in].   */
@@ -1144,6 +1187,14 @@ int vt_contact_scan(const float *depth, const double *depth_origin, const unsign
 int vt_contact_points(const float *depth, const int *index, const int *sel, const int *kept, const int *row0, const double *pose,
                       int n_images, int n_pixels, int width, int height, double fov_deg, int max_points, int S,
                       float *p_sample, long long *finger, void *stream);
+
+/* vt_depth_cloud: EVERY pixel of the predicted depth images as a world-space point (Generator3D.generate_tactile_pc,             */
+/*   src/conv_onet/generation.py:286-333): pred [n_images][n_pixels] f32 (the depth estimator's sigmoid output); depth = pred *      */
+/*   0.005f + 0.019f in float32 (numpy on a float32 array), then vt_contact_points' unprojection, pose and normalisation in float64   */
+/*   with the same pose records [n_images][16] -> out [n_images][n_pixels][3], float64 (what the reference returns) or, with          */
+/*   out_f32 != 0, float32.                                                                                                           */
+int vt_depth_cloud(const float *pred, const double *pose, int n_images, int n_pixels, int width, int height, double fov_deg,
+                   void *out, int out_f32, void *stream);
 
 /* Evaluation metrics of the visualise block: the reference's generate_obj_mesh_wnf ends with                                   */
 /*   cd = chamfer_distance(points_obj, vertices[:2048], use_kdtree=False); emd = EarthMoverDistance(points_obj[0], vertices)     */

@@ -116,6 +116,20 @@ class ResnetParams(ctypes.Structure):
                 ("linear_w", ctypes.c_void_p), ("linear_b", ctypes.c_void_p), ("fc_w", ctypes.c_void_p), ("fc_b", ctypes.c_void_p)]
 
 
+VT_TACTILE_UNET_MAX_DEPTH = 5
+VT_TACTILE_UNET_MAX_CLASSES = 4
+
+
+class TactileUnetParams(ctypes.Structure):
+    """Mirror of ``vt_tactile_unet_params``."""
+    _D = VT_TACTILE_UNET_MAX_DEPTH
+    _fields_ = [("depth", ctypes.c_int32), ("start_filts", ctypes.c_int32), ("in_channels", ctypes.c_int32), ("num_classes", ctypes.c_int32),
+                ("down_w", (ctypes.c_void_p * 2) * _D), ("down_b", (ctypes.c_void_p * 2) * _D), ("down_bn", ResnetBn * _D),
+                ("up_tw", ctypes.c_void_p * _D), ("up_tb", ctypes.c_void_p * _D),
+                ("up_w", (ctypes.c_void_p * 2) * _D), ("up_b", (ctypes.c_void_p * 2) * _D), ("up_bn", ResnetBn * _D),
+                ("final_w", ctypes.c_void_p), ("final_b", ctypes.c_void_p)]
+
+
 # name -> (restype, argtypes); kept in step with include/vtaco_hip.h (tests/test_abi.py
 # parses the header and checks that every declared symbol is exported and listed here)
 _VP, _I, _I64, _F, _D, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
@@ -242,6 +256,12 @@ SIGNATURES = {
     "vt_resnet_workspace_bytes": (_SZ, [ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I]),
     "vt_resnet_pack": (_I, [ctypes.POINTER(ResnetParams), _VP, _SZ, _VP]),
     "vt_resnet_fwd": (_I, [_VP, _I, _I, _I, ctypes.POINTER(ResnetParams), _VP, _VP, _SZ, _VP, _VP]),
+    "vt_tactile_unet_supported": (_I, [_I, _I, _I, _I, _I, _I, _I]),
+    "vt_tactile_unet_blob_bytes": (_SZ, [_I, _I, _I, _I]),
+    "vt_tactile_unet_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
+    "vt_tactile_unet_pack": (_I, [ctypes.POINTER(TactileUnetParams), _VP, _SZ, _VP]),
+    "vt_tactile_unet_fwd": (_I, [_VP, _I, _I, _I, ctypes.POINTER(TactileUnetParams), _VP, _VP, _SZ, _VP, _VP]),
+    "vt_depth_cloud": (_I, [_VP, _VP, _I, _I, _I, _I, _D, _VP, _I, _VP]),
     "vt_plane_unet_bwd_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
     "vt_plane_unet_bwd": (_I, [_VP, _I, _I, _I, ctypes.POINTER(PlaneUnetParams), _VP, _VP, _VP, _VP, _SZ, ctypes.POINTER(PlaneUnetGrads), _VP, _VP]),
     "vt_mano_pack": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),

@@ -124,6 +124,23 @@ def contact_clouds_from_depth(depths, depth_origin, cam_pos, cam_rot, pc_ply, to
     return anchors, count
 
 
+def sensor_pose_records(cam_pos, cam_rot, pc_ply, touch=None):
+    """The pose records [B * 5, 16] float64 that vt_contact_points / vt_depth_cloud read: per sensor the inverse pose's 3 x 3 (row-major),
+    the translation, the scene's cloud centroid and scale (``sensor_pose_inverse``, ``cloud_norm``).  ``touch`` [B,5] bool or None: a
+    sensor that did not touch keeps a zero pose.  Host side: 5 B inverses of a 4 x 4 and B passes over the object clouds."""
+    import numpy as np
+    B = len(pc_ply)
+    pose = np.zeros((B * 5, 16))
+    for b in range(B):
+        centroid, scale = cloud_norm(pc_ply[b])
+        for t in range(5):
+            if touch is None or touch[b, t]:
+                m_inv, trans = sensor_pose_inverse(cam_pos[b][t], cam_rot[b][t])
+                pose[b * 5 + t, :9], pose[b * 5 + t, 9:12] = m_inv.reshape(-1), trans
+            pose[b * 5 + t, 12:15], pose[b * 5 + t, 15] = centroid, scale
+    return pose
+
+
 def contact_clouds_on_device(depths_dev, origin_dev, cam_pos, cam_rot, pc_ply, touch_success, p_sample_host, p_host, num_sample,
                              width=240, height=320, fov=60.0, max_points=128, threshold=1e-4, pack=True):
     """The batch form of ``contact_clouds_from_depth`` + the VTacO step's row assembly (training.py:809-866) with the pixel work on the
@@ -144,14 +161,7 @@ def contact_clouds_on_device(depths_dev, origin_dev, cam_pos, cam_rot, pc_ply, t
     touch = np.asarray(touch_success).astype(bool).reshape(B, 5)
     index, count = ops.contact_scan(depths_dev.reshape(B * 5, -1), origin_dev, torch.from_numpy(touch.astype(np.uint8).reshape(-1)).to(dev), threshold)
     # the host side that does not depend on the counts runs while the scan does
-    pose = np.zeros((B * 5, 16))
-    for b in range(B):
-        centroid, scale = cloud_norm(pc_ply[b])
-        for t in range(5):
-            if touch[b, t]:
-                m_inv, trans = sensor_pose_inverse(cam_pos[b][t], cam_rot[b][t])
-                pose[b * 5 + t, :9], pose[b * 5 + t, 9:12] = m_inv.reshape(-1), trans
-            pose[b * 5 + t, 12:15], pose[b * 5 + t, 15] = centroid, scale
+    pose = sensor_pose_records(cam_pos, cam_rot, pc_ply, touch)
     cnt = count.cpu().numpy().reshape(B, 5)                          # the one synchronisation of the assembly: 5 B integers
     sel = np.zeros((B * 5, max_points), dtype=np.int32)
     kept = np.zeros(B * 5, dtype=np.int32)

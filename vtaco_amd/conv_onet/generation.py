@@ -644,6 +644,34 @@ class Generator3D(object):
         v = (v - centroid.double()) / (2.0 * m.double())
         return Mesh(v, c_hand['mano_faces'])
 
+    def generate_tactile_pc(self, data, fov=60.0):
+        """The tactile model's inference output (generation.py:286-333): every pixel of the five predicted depth images of each scene
+        as a point of the object's normalised frame.  ``data``: 'inputs.img' [B,5,C,H,W], 'points.cam_pos' / 'points.cam_rot' (the
+        sensors' poses, [B,5,3] or [B,15]), 'inputs.pc_ply' [B,T,3], 'points.name'.  Returns (pc_world_l, data_name): a float64 numpy
+        array [B, 5, H*W, 3] and the names, as the reference does.  The depth estimator runs on all B * 5 images at once
+        (encode_img_inputs); depth = pred * 0.005 + 0.019, the pinhole unprojection, the pose (rotation + [-pi/2, 0, pi/2]) and
+        norm_pc_1 run per pixel on the device (vt_depth_cloud); the host prepares the 5 B pose inverses and the clouds' centroid and
+        scale (sensor_pose_records).  H and W come from the images (the reference hard-codes 320 x 240).  The reference also calls
+        encode_hand_inputs here and uses nothing of its result: that call is not made."""
+        from ..common import sensor_pose_records
+        if getattr(self.model, 'encoder_img', None) is None:
+            raise VtError("generate_tactile_pc: the model needs encoder_img (the tactile depth estimator)")
+        self._eval_mode()
+        imgs = data.get('inputs.img').to(self.device)
+        if imgs.dim() != 5 or imgs.shape[1] != 5:
+            raise VtError(f"generate_tactile_pc: inputs.img must be [B, 5, C, H, W] (got {tuple(imgs.shape)})")
+        B, Fn, _, H, W = imgs.shape
+        cam_pos = data.get('points.cam_pos').detach().cpu().numpy().reshape(B, 5, 3)
+        cam_rot = data.get('points.cam_rot').detach().cpu().numpy().reshape(B, 5, 3)
+        pc_ply = data.get('inputs.pc_ply').detach().cpu().numpy()
+        with torch.no_grad():
+            pred = self.model.encode_img_inputs(imgs)
+            if pred.shape[0] != B or pred.numel() != B * Fn * H * W:
+                raise VtError(f"generate_tactile_pc: the depth estimator must give one value per pixel (got {tuple(pred.shape)}: num_classes 1?)")
+            pose = torch.from_numpy(sensor_pose_records(cam_pos, cam_rot, pc_ply)).to(self.device)
+            cloud = ops.depth_cloud(pred.reshape(B * Fn, H * W).float(), pose, W, H, fov)
+        return cloud.view(B, Fn, H * W, 3).cpu().numpy(), data.get('points.name')
+
     def generate_obj_mesh_wnf(self, data, c_img_all=None):
         """Encode -> dense decode -> marching cubes for one scene; ``data['inputs']`` is the
         point cloud [1,T,3].  Returns Mesh(vertices [V,3] f32, faces [F,3] i32) on the device -- or, with

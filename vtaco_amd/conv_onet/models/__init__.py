@@ -57,12 +57,12 @@ class ConvolutionalOccupancyNetwork(nn.Module):
             return torch.empty(imgs.size(0), 0)
         B, Fn = imgs.shape[:2]
         enc = self.encoder_img
-        if B > 1 and hasattr(enc, "hip_supported") and hasattr(enc, "forward_scenes"):
+        if B > 1 and hasattr(enc, "hip_supported"):
             # eval mode on the HIP kernels: an image's features do not depend on its batch (bit for bit), so all B * Fn images go
             # in one call whatever VTACO_TACTILE_SCENE_BATCH says (that knob is about train-mode statistics)
             flat = imgs.reshape(B * Fn, *imgs.shape[2:])
             if enc.hip_supported(flat):
-                return enc(flat).view(B, Fn, -1)
+                return enc(flat).view(B, Fn, -1)                     # (the depth U-Net's [B * Fn, 1, H, W] as [B, Fn, H * W] alike)
         if B > 1 and _SCENE_BATCH and hasattr(self.encoder_img, "forward_scenes"):
             return self.encoder_img.forward_scenes(imgs)             # the same values from one pass over the B * Fn images
         return torch.cat([self.encoder_img(imgs[b]).reshape(1, Fn, -1) for b in range(B)], dim=0)

@@ -46,6 +46,33 @@ contact_scan_kernel(const float *depth, const double *origin, const unsigned cha
 
 struct ContactPose { double m[9], t[3], centroid[3], scale; };         // inverse pose's linear part, translation; norm_pc_1 of the scene
 
+// pixel (px, py) at depth z -> the object's normalised frame, float64 in the reference's operation order:
+// cam = (z, -(px - w/2) z / f, -(py - h/2) z / f) as numpy evaluates it, ((-(px - w/2)) * z) / f; world = M cam + t; (world - centroid) / scale
+__device__ __forceinline__ void contact_world_point(const ContactPose &ps, double z, int px, int py, int width, int height, double f, double (&out)[3]) {
+    const double c0 = z, c1 = (-((double)px - width / 2.0)) * z / f, c2 = (-((double)py - height / 2.0)) * z / f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double w = fma(ps.m[3 * i + 2], c2, fma(ps.m[3 * i + 1], c1, ps.m[3 * i] * c0)) + ps.t[i];
+        out[i] = (w - ps.centroid[i]) / ps.scale;
+    }
+}
+
+// every pixel of every image (generate_tactile_pc): depth = pred * 0.005f + 0.019f in float32, then the same point rule
+template <typename T>
+__global__ void __launch_bounds__(256)
+depth_cloud_kernel(const float *pred, const ContactPose *pose, int npix, int width, int height, double f, T *out) {
+    const int img = blockIdx.y;
+    const ContactPose ps = pose[img];
+    for (int pix = blockIdx.x * 256 + threadIdx.x; pix < npix; pix += gridDim.x * 256) {
+        const float depth = pred[(size_t)img * npix + pix] * 0.005f + 0.019f;       // (-ffp-contract=off: two roundings, like numpy)
+        double w[3];
+        contact_world_point(ps, (double)depth, pix % width, pix / width, width, height, f, w);
+        T *o = out + ((size_t)img * npix + pix) * 3;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) o[i] = (T)w[i];
+    }
+}
+
 __global__ void __launch_bounds__(256)
 contact_points_kernel(const float *depth, const int *index, const int *sel, const int *kept, const int *row0, const ContactPose *pose,
                       int npix, int width, int height, double f, int max_points, int S, float *p_sample, long long *finger) {
@@ -56,15 +83,11 @@ contact_points_kernel(const float *depth, const int *index, const int *sel, cons
         const int s = sel ? sel[(size_t)img * max_points + j] : j;
         const int pix = index[(size_t)img * npix + s];
         const int px = pix % width, py = pix / width;
-        const double z = (double)depth[(size_t)img * npix + pix];
-        // cam = (z, -(px - w/2) z / f, -(py - h/2) z / f) as numpy evaluates it: ((-(px - w/2)) * z) / f
-        const double c0 = z, c1 = (-((double)px - width / 2.0)) * z / f, c2 = (-((double)py - height / 2.0)) * z / f;
         double w[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) w[i] = fma(ps.m[3 * i + 2], c2, fma(ps.m[3 * i + 1], c1, ps.m[3 * i] * c0)) + ps.t[i];
+        contact_world_point(ps, (double)depth[(size_t)img * npix + pix], px, py, width, height, f, w);
         const size_t row = (size_t)b * S + row0[img] + j;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) p_sample[row * 3 + i] = (float)((w[i] - ps.centroid[i]) / ps.scale);
+        for (int i = 0; i < 3; ++i) p_sample[row * 3 + i] = (float)w[i];
         if (finger) finger[row] = t;
     }
 }
@@ -92,6 +115,19 @@ int vt_contact_points(const float *depth, const int *index, const int *sel, cons
     hipLaunchKernelGGL(contact_points_kernel, dim3((unsigned)n_images), dim3(256), 0, (hipStream_t)stream, depth, index, sel, kept, row0,
                        reinterpret_cast<const ContactPose *>(pose), n_pixels, width, height, f, max_points, S, p_sample, finger);
     return vt_check(hipGetLastError(), "vt_contact_points");
+}
+
+int vt_depth_cloud(const float *pred, const double *pose, int n_images, int n_pixels, int width, int height, double fov_deg,
+                   void *out, int out_f32, void *stream) {
+    if (n_images == 0) return 0;
+    if (!pred || !pose || !out || n_images < 0 || n_images > 65535 || width <= 0 || height <= 0 || (long long)width * height != n_pixels)
+        return vt_fail(VT_ERR_INVALID, "vt_depth_cloud: bad argument");
+    const double f = height / (2.0 * tan(fov_deg * 3.14159265358979323846 / 180.0 / 2.0));
+    const dim3 grid((unsigned)((n_pixels + 255) / 256 < 1024 ? (n_pixels + 255) / 256 : 1024), (unsigned)n_images);
+    const ContactPose *ps = reinterpret_cast<const ContactPose *>(pose);
+    if (out_f32) hipLaunchKernelGGL(depth_cloud_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, pred, ps, n_pixels, width, height, f, (float *)out);
+    else hipLaunchKernelGGL(depth_cloud_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, pred, ps, n_pixels, width, height, f, (double *)out);
+    return vt_check(hipGetLastError(), "vt_depth_cloud");
 }
 
 }  // extern "C"

@@ -25,6 +25,17 @@ def _tactile_resnet_mode():
     return mode
 
 
+# the eval-mode forward of TactileUNet: "hip" = vt_tactile_unet_fwd (csrc/unet2d.hip), "host" = the nn modules (MIOpen); read at every call
+_TACTILE_UNET_DEFAULT = "hip"
+
+
+def _tactile_unet_mode():
+    mode = os.environ.get("VTACO_TACTILE_UNET", _TACTILE_UNET_DEFAULT)
+    if mode not in ("hip", "host"):
+        raise ValueError(f"VTACO_TACTILE_UNET must be 'hip' or 'host' (got {mode!r})")
+    return mode
+
+
 class _TallLinear(torch.autograd.Function):
     """nn.Linear over a tall, skinny activation matrix ([tens of thousands of points] x [32..64 channels]) whose weight
     gradient dW = dy^T x is a 32 x 64 GEMM with K = 24 000: hipBLASLt runs that as one workgroup-starved kernel (0.5 ms,
@@ -121,7 +132,10 @@ class UpConv(_ConvPair):
 class TactileUNet(nn.Module):
     """Tactile depth estimator (reference ``UNet``, src/layers.py:322-450): `depth`
     DownConvs (last without pooling), depth-1 UpConvs (transpose-conv up, concat),
-    1x1 conv, sigmoid.  Host PyTorch-ROCm."""
+    1x1 conv, sigmoid.  In eval mode without autograd on a HIP f32 input the forward is ``vt_tactile_unet_fwd`` (csrc/unet2d.hip:
+    BatchNorm folded into the convs, pool / concat / conv_final / sigmoid fused into them, 12 launches at depth 3, bit-reproducible and
+    batch-invariant); train mode, anything under autograd and ``VTACO_TACTILE_UNET=host`` run the nn modules (``forward_modules``:
+    host PyTorch-ROCm / MIOpen)."""
 
     def __init__(self, num_classes=1, in_channels=3, depth=4, start_filts=32, up_mode='transpose',
                  merge_mode='concat', **kwargs):
@@ -139,7 +153,38 @@ class TactileUNet(nn.Module):
                 nn.init.xavier_normal_(m.weight)
                 nn.init.constant_(m.bias, 0)
 
+    def hip_supported(self, x):
+        """Eval mode, no autograd through the call, a HIP f32 image batch, a shape vt_tactile_unet_supported covers."""
+        if self.training or _tactile_unet_mode() != "hip" or not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False
+        return x.shape[1] == self.in_channels and x.shape[0] > 0 and ops.tactile_unet_supported(self, x.shape[0], x.shape[2], x.shape[3])
+
+    def _blob_stamp(self):
+        """(storage, version) of every parameter AND buffer: load_state_dict, an optimiser step and a train-mode forward (running
+        statistics) all change it."""
+        return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+
+    def _blob(self):
+        """The packed weights (BatchNorm folded in), repacked when the stamp moved.  Generator3D runs every stage eagerly before it
+        captures it, so the packing launches never fall inside a stream capture."""
+        stamp = self._blob_stamp()
+        hit = self.__dict__.get("_blob_cache")
+        if hit is None or hit[0] != stamp:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("TactileUNet: weights changed since the last eager call; run one eval forward outside stream capture")
+            hit = (stamp, ops.tactile_unet_pack(self))
+            self.__dict__["_blob_cache"] = hit
+        return hit[1]
+
     def forward(self, x):
+        if self.hip_supported(x):
+            return ops.tactile_unet_fwd(x, self, self._blob())
+        return self.forward_modules(x)
+
+    def forward_modules(self, x):
+        """The nn modules one by one (host PyTorch-ROCm / MIOpen): train mode, autograd, shapes the HIP path does not cover."""
         skips = []
         for down in self.down_convs:
             x, skip = down(x)

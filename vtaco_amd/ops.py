@@ -2236,6 +2236,112 @@ def resnet_fwd(x, net, blob, ws=None):
     return out
 
 
+# ---- the tactile depth estimator in eval mode (unet2d.hip) ---------------------------------------------------------------------------
+
+def _tactile_unet_dims(net):
+    return int(net.depth), int(net.start_filts), int(net.in_channels), int(net.num_classes)
+
+
+def tactile_unet_supported(net, n_img, H, W):
+    return bool(_lib.load().vt_tactile_unet_supported(*_tactile_unet_dims(net), int(n_img), int(H), int(W)))
+
+
+def tactile_unet_params(net):
+    """(TactileUnetParams, tensors it points to) of a ``layers.TactileUNet``: every conv's weight and bias, each block's ONE BatchNorm
+    (weight, bias, running statistics, eps), the transposed convs and conv_final, in the state_dict's own layouts."""
+    prm = _lib.TactileUnetParams()
+    prm.depth, prm.start_filts, prm.in_channels, prm.num_classes = _tactile_unet_dims(net)
+    keep = []
+
+    def ptr(t, name):
+        t = _c(t)
+        keep.append(t)
+        return dev_ptr(t, name).value
+
+    def pair(w, b, bn, i, blk, name):
+        if blk.bn.weight is None or blk.bn.running_mean is None:
+            raise VtError(f"tactile_unet_pack: {name}.bn has no affine parameters or no running statistics")
+        for k, conv in enumerate((blk.conv1, blk.conv2)):
+            w[i][k], b[i][k] = ptr(conv.weight, f"{name}.conv{k + 1}.weight"), ptr(conv.bias, f"{name}.conv{k + 1}.bias")
+        bn[i].weight, bn[i].bias = ptr(blk.bn.weight, name + ".bn.weight"), ptr(blk.bn.bias, name + ".bn.bias")
+        bn[i].running_mean, bn[i].running_var = ptr(blk.bn.running_mean, name + ".bn.running_mean"), ptr(blk.bn.running_var, name + ".bn.running_var")
+        bn[i].eps = float(blk.bn.eps)
+    for i, blk in enumerate(net.down_convs):
+        pair(prm.down_w, prm.down_b, prm.down_bn, i, blk, f"down_convs.{i}")
+    for j, blk in enumerate(net.up_convs):
+        i = prm.depth - 2 - j                                         # the level this block produces
+        pair(prm.up_w, prm.up_b, prm.up_bn, i, blk, f"up_convs.{j}")
+        prm.up_tw[i], prm.up_tb[i] = ptr(blk.upconv.weight, f"up_convs.{j}.upconv.weight"), ptr(blk.upconv.bias, f"up_convs.{j}.upconv.bias")
+    prm.final_w, prm.final_b = ptr(net.conv_final.weight, "conv_final.weight"), ptr(net.conv_final.bias, "conv_final.bias")
+    return prm, keep
+
+
+def tactile_unet_pack(net):
+    """The net's convs with their BatchNorms folded in, in fragment order: the blob vt_tactile_unet_fwd reads (vt_tactile_unet_pack)."""
+    lib = _lib.load()
+    n = lib.vt_tactile_unet_blob_bytes(*_tactile_unet_dims(net))
+    if n == 0:
+        raise VtError("tactile U-Net not built for this net (vt_tactile_unet_supported)")
+    prm, keep = tactile_unet_params(net)
+    blob = torch.empty(n // 4, dtype=torch.float32, device=keep[0].device)
+    check(lib.vt_tactile_unet_pack(ctypes.byref(prm), dev_ptr(blob, "blob"), n, stream_ptr()), "vt_tactile_unet_pack")
+    return blob
+
+
+_tactile_unet_ws = {}  # (device, stream, dims, images, H, W) -> workspace; at most _RESNET_WS_MAX entries, the oldest leaves first
+
+
+def tactile_unet_workspace(net, n_img, H, W):
+    """Workspace of vt_tactile_unet_fwd, one per (device, STREAM, shape), like resnet_workspace."""
+    lib = _lib.load()
+    dev = torch.cuda.current_device()
+    key = (dev, torch.cuda.current_stream().cuda_stream, _tactile_unet_dims(net), int(n_img), int(H), int(W))
+    ws = _tactile_unet_ws.get(key)
+    if ws is None:
+        n = lib.vt_tactile_unet_workspace_bytes(*_tactile_unet_dims(net), int(n_img), int(H), int(W))
+        if n == 0:
+            raise VtError("tactile U-Net shape not built (vt_tactile_unet_supported)")
+        ws = torch.empty(n, dtype=torch.uint8, device=torch.device("cuda", dev))
+        while len(_tactile_unet_ws) >= _RESNET_WS_MAX:
+            _tactile_unet_ws.pop(next(iter(_tactile_unet_ws)))
+        _tactile_unet_ws[key] = ws
+    keep_for_graph(ws)
+    return ws
+
+
+def tactile_unet_fwd(x, net, blob, ws=None):
+    """TactileUNet.forward in eval mode on the HIP kernels: x [n_img, in_channels, H, W] -> [n_img, num_classes, H, W] (vt_tactile_unet_fwd)."""
+    x = _c(x)
+    if x.dim() != 4 or x.shape[1] != net.in_channels:
+        raise VtError(f"tactile_unet_fwd: input must be [n_img, {net.in_channels}, H, W] (got {tuple(x.shape)})")
+    n_img, _, H, W = x.shape
+    if ws is None:
+        ws = tactile_unet_workspace(net, n_img, H, W)
+    prm = _lib.TactileUnetParams()
+    prm.depth, prm.start_filts, prm.in_channels, prm.num_classes = _tactile_unet_dims(net)
+    out = torch.empty((n_img, prm.num_classes, H, W), dtype=torch.float32, device=x.device)
+    keep_for_graph(blob, x)
+    check(_lib.load().vt_tactile_unet_fwd(dev_ptr(x, "x"), n_img, H, W, ctypes.byref(prm), dev_ptr(blob, "blob"),
+                                          ctypes.c_void_p(ws.data_ptr()), ws.numel(), dev_ptr(out, "out"), stream_ptr()), "vt_tactile_unet_fwd")
+    return out
+
+
+def depth_cloud(pred, pose, width, height, fov=60.0, dtype=torch.float64):
+    """Every pixel of the predicted depth images as a point of the object's normalised frame (vt_depth_cloud): pred [n_images, H*W] f32
+    (the depth estimator's output), pose [n_images, 16] f64 (inverse pose 3 x 3, translation, cloud centroid, scale: the records of
+    ``contact_points``) -> [n_images, H*W, 3] float64 (or float32)."""
+    if dtype not in (torch.float64, torch.float32):
+        raise VtError("depth_cloud: dtype must be float64 or float32")
+    pred = _c(pred)
+    n_img, n_pix = pred.shape
+    if tuple(pose.shape) != (n_img, 16) or int(width) * int(height) != n_pix:
+        raise VtError(f"depth_cloud: pred {tuple(pred.shape)} needs pose [{n_img}, 16] and width * height = {n_pix}")
+    out = torch.empty((n_img, n_pix, 3), dtype=dtype, device=pred.device)
+    check(_lib.load().vt_depth_cloud(dev_ptr(pred, "pred"), dev_ptr(pose, "pose", torch.float64), n_img, n_pix, int(width), int(height),
+                                     float(fov), ctypes.c_void_p(out.data_ptr()), 1 if dtype == torch.float32 else 0, stream_ptr()), "vt_depth_cloud")
+    return out
+
+
 def plane_unet_bwd(x, net, blob, fwd_ws, dout):
     """Backward of plane_unet_fwd (vt_plane_unet_bwd): (dx, {parameter name: gradient}) from dout, the input, the packed weights and the
     workspace the forward filled.  Gradients are written, not accumulated."""
