@@ -1101,6 +1101,49 @@ int vt_tactile_unet_fwd(const float *x, int n_img, int H, int W, const vt_tactil
                         void *workspace, size_t workspace_bytes, float *out, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Tactile depth estimator, train mode: forward with batch statistics and the      */
+/*   backward for every parameter (unet2d_train.hip).                              */
+/* x [n_img][in_channels][H][W], scene-major: images s * group .. s * group +      */
+/*   group - 1 are one statistics group (the reference calls the net once per      */
+/*   scene on its 5 images).  Every 3x3 conv is z = conv(x) + b, the per-group,    */
+/*   per-channel mean and biased variance of z, relu(gamma (z - mean) /            */
+/*   sqrt(var + eps) + beta); a block's ONE BatchNorm follows both convs (shared   */
+/*   gamma, beta; statistics per use).  The raw weights of params_host are packed  */
+/*   at every call; no blob.  momentum >= 0: the running_mean / running_var the    */
+/*   params point to are UPDATED in place, per block for each scene in order and   */
+/*   per scene conv1's use then conv2's: running = (1 - m) running + m batch       */
+/*   (unbiased variance); momentum < 0 leaves them alone.  num_batches_tracked     */
+/*   (+ 2 * n_img / group per block) is the caller's.                              */
+/* vt_tactile_unet_bwd: from dout [n_img][num_classes][H][W], the forward's out    */
+/*   and the workspace the forward filled (same shape, same params), the gradient  */
+/*   of every parameter (vt_tactile_unet_grads: written, not accumulated; gamma    */
+/*   and beta of a block are the sum over its two uses).  No gradient for x.       */
+/* Exact-f32 matrix core for the convs, their data and weight gradients; the       */
+/*   per-channel sums and the weight gradients' partials are combined in f64 in a  */
+/*   fixed order that depends on neither the number of scenes nor the launch: no   */
+/*   atomics, bit-reproducible, a scene's outputs do not depend on the others.     */
+/* Covered (vt_tactile_unet_train_supported): what vt_tactile_unet_supported       */
+/*   covers with start_filts 8, 16, 32 or 64; group >= 1 dividing n_img; at least  */
+/*   2 values per group and channel at the bottom level.  Unsupported: the size    */
+/*   query returns 0.  The workspace keeps every conv's z and activation for the   */
+/*   backward: about 20 level-0 activations (n_img * H * W * start_filts floats).  */
+/* ------------------------------------------------------------------------- */
+typedef struct vt_tactile_unet_grads {
+    float *down_w[VT_TACTILE_UNET_MAX_DEPTH][2], *down_b[VT_TACTILE_UNET_MAX_DEPTH][2];
+    float *down_bn_w[VT_TACTILE_UNET_MAX_DEPTH], *down_bn_b[VT_TACTILE_UNET_MAX_DEPTH];         /* down_convs[i].bn weight (gamma), bias (beta) */
+    float *up_tw[VT_TACTILE_UNET_MAX_DEPTH], *up_tb[VT_TACTILE_UNET_MAX_DEPTH];
+    float *up_w[VT_TACTILE_UNET_MAX_DEPTH][2], *up_b[VT_TACTILE_UNET_MAX_DEPTH][2];
+    float *up_bn_w[VT_TACTILE_UNET_MAX_DEPTH], *up_bn_b[VT_TACTILE_UNET_MAX_DEPTH];
+    float *final_w, *final_b;
+} vt_tactile_unet_grads;
+int vt_tactile_unet_train_supported(int depth, int start_filts, int in_channels, int num_classes, int n_img, int group, int H, int W);
+size_t vt_tactile_unet_train_workspace_bytes(int depth, int start_filts, int in_channels, int num_classes, int n_img, int group, int H, int W);
+int vt_tactile_unet_train_fwd(const float *x, int n_img, int group, int H, int W, const vt_tactile_unet_params *params_host, double momentum,
+                              void *workspace, size_t workspace_bytes, float *out, void *stream);
+int vt_tactile_unet_bwd(const float *dout, const float *out, int n_img, int group, int H, int W, const vt_tactile_unet_params *params_host,
+                        void *workspace, size_t workspace_bytes, const vt_tactile_unet_grads *grads_host, void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* PointNet per-point MLP (inference).  Replaces the nn.Linear / ResnetBlockFC   */
 /* calls of LocalPoolPointnet.forward (src/encoder/pointnet.py:154-162;           */
 /* src/layers.py:8-50): rows are points, weights in nn.Linear layout [out][in].   */

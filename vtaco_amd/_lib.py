@@ -130,6 +130,17 @@ class TactileUnetParams(ctypes.Structure):
                 ("final_w", ctypes.c_void_p), ("final_b", ctypes.c_void_p)]
 
 
+class TactileUnetGrads(ctypes.Structure):
+    """Mirror of ``vt_tactile_unet_grads``."""
+    _D = VT_TACTILE_UNET_MAX_DEPTH
+    _fields_ = [("down_w", (ctypes.c_void_p * 2) * _D), ("down_b", (ctypes.c_void_p * 2) * _D),
+                ("down_bn_w", ctypes.c_void_p * _D), ("down_bn_b", ctypes.c_void_p * _D),
+                ("up_tw", ctypes.c_void_p * _D), ("up_tb", ctypes.c_void_p * _D),
+                ("up_w", (ctypes.c_void_p * 2) * _D), ("up_b", (ctypes.c_void_p * 2) * _D),
+                ("up_bn_w", ctypes.c_void_p * _D), ("up_bn_b", ctypes.c_void_p * _D),
+                ("final_w", ctypes.c_void_p), ("final_b", ctypes.c_void_p)]
+
+
 # name -> (restype, argtypes); kept in step with include/vtaco_hip.h (tests/test_abi.py
 # parses the header and checks that every declared symbol is exported and listed here)
 _VP, _I, _I64, _F, _D, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
@@ -261,6 +272,10 @@ SIGNATURES = {
     "vt_tactile_unet_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
     "vt_tactile_unet_pack": (_I, [ctypes.POINTER(TactileUnetParams), _VP, _SZ, _VP]),
     "vt_tactile_unet_fwd": (_I, [_VP, _I, _I, _I, ctypes.POINTER(TactileUnetParams), _VP, _VP, _SZ, _VP, _VP]),
+    "vt_tactile_unet_train_supported": (_I, [_I, _I, _I, _I, _I, _I, _I, _I]),
+    "vt_tactile_unet_train_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I, _I]),
+    "vt_tactile_unet_train_fwd": (_I, [_VP, _I, _I, _I, _I, ctypes.POINTER(TactileUnetParams), _D, _VP, _SZ, _VP, _VP]),
+    "vt_tactile_unet_bwd": (_I, [_VP, _VP, _I, _I, _I, _I, ctypes.POINTER(TactileUnetParams), _VP, _SZ, ctypes.POINTER(TactileUnetGrads), _VP]),
     "vt_depth_cloud": (_I, [_VP, _VP, _I, _I, _I, _I, _D, _VP, _I, _VP]),
     "vt_plane_unet_bwd_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
     "vt_plane_unet_bwd": (_I, [_VP, _I, _I, _I, ctypes.POINTER(PlaneUnetParams), _VP, _VP, _VP, _VP, _SZ, ctypes.POINTER(PlaneUnetGrads), _VP, _VP]),

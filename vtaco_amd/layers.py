@@ -36,6 +36,48 @@ def _tactile_unet_mode():
     return mode
 
 
+# the train-mode forward and backward of TactileUNet under autograd: "hip" = vt_tactile_unet_train_fwd / vt_tactile_unet_bwd
+# (csrc/unet2d_train.hip), "host" = the nn modules (MIOpen); read at every call
+_TACTILE_UNET_TRAIN_DEFAULT = "host"
+
+
+def _tactile_unet_train_mode():
+    mode = os.environ.get("VTACO_TACTILE_UNET_TRAIN", _TACTILE_UNET_TRAIN_DEFAULT)
+    if mode not in ("hip", "host"):
+        raise ValueError(f"VTACO_TACTILE_UNET_TRAIN must be 'hip' or 'host' (got {mode!r})")
+    return mode
+
+
+class _TactileUNetTrain(torch.autograd.Function):
+    """TactileUNet.forward in train mode under autograd on the HIP kernels: ops.tactile_unet_train_fwd, ops.tactile_unet_bwd.  ``params``
+    = the net's parameters in named_parameters() order (autograd inputs, so the optimiser's tensors receive the gradients); x gets
+    none.  The workspace is shared per (device, stream, shape): if another forward of that shape ran before this call's backward, the
+    backward first runs the forward again (running statistics untouched)."""
+
+    @staticmethod
+    def forward(ctx, x, net, scenes, *params):
+        n_img, _, H, W = x.shape
+        ws = ops.tactile_unet_train_workspace(net, n_img, n_img // scenes, H, W)
+        out = ops.tactile_unet_train_fwd(x, net, scenes, momentum=float(net.down_convs[0].bn.momentum), ws=ws)
+        with torch.no_grad():
+            for blk in list(net.down_convs) + list(net.up_convs):
+                blk.bn.num_batches_tracked += 2 * scenes             # (also moves the eval path's blob stamp: the kernel wrote the statistics)
+        ctx.net, ctx.scenes, ctx.ws, ctx.gen = net, scenes, ws, ws.gen
+        ctx.save_for_backward(x, out, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, out = ctx.saved_tensors[:2]                               # (raises if a parameter changed since the forward)
+        net = ctx.net
+        if ctx.ws.gen != ctx.gen:
+            ops.tactile_unet_train_fwd(x, net, ctx.scenes, momentum=None, ws=ctx.ws)
+            ctx.gen = ctx.ws.gen
+        grads = ops.tactile_unet_bwd(dout, out, net, ctx.scenes, ctx.ws)
+        return (None, None, None) + tuple(grads[name] if need else None
+                                          for (name, _), need in zip(net.named_parameters(), ctx.needs_input_grad[3:]))
+
+
 class _TallLinear(torch.autograd.Function):
     """nn.Linear over a tall, skinny activation matrix ([tens of thousands of points] x [32..64 channels]) whose weight
     gradient dW = dy^T x is a 32 x 64 GEMM with K = 24 000: hipBLASLt runs that as one workgroup-starved kernel (0.5 ms,
@@ -134,8 +176,10 @@ class TactileUNet(nn.Module):
     DownConvs (last without pooling), depth-1 UpConvs (transpose-conv up, concat),
     1x1 conv, sigmoid.  In eval mode without autograd on a HIP f32 input the forward is ``vt_tactile_unet_fwd`` (csrc/unet2d.hip:
     BatchNorm folded into the convs, pool / concat / conv_final / sigmoid fused into them, 12 launches at depth 3, bit-reproducible and
-    batch-invariant); train mode, anything under autograd and ``VTACO_TACTILE_UNET=host`` run the nn modules (``forward_modules``:
-    host PyTorch-ROCm / MIOpen)."""
+    batch-invariant).  In train mode under autograd with ``VTACO_TACTILE_UNET_TRAIN=hip`` the forward and the backward are
+    ``vt_tactile_unet_train_fwd`` / ``vt_tactile_unet_bwd`` (csrc/unet2d_train.hip: batch statistics per scene, every parameter's
+    gradient, bit-reproducible; ``train_hip_supported``).  Everything else runs the nn modules (``forward_modules``: host
+    PyTorch-ROCm / MIOpen)."""
 
     def __init__(self, num_classes=1, in_channels=3, depth=4, start_filts=32, up_mode='transpose',
                  merge_mode='concat', **kwargs):
@@ -178,10 +222,43 @@ class TactileUNet(nn.Module):
             self.__dict__["_blob_cache"] = hit
         return hit[1]
 
-    def forward(self, x):
+    def train_hip_supported(self, x, scenes=1):
+        """Train mode with autograd on, a parameter that requires grad, a HIP f32 image batch that does not, VTACO_TACTILE_UNET_TRAIN=hip,
+        ordinary BatchNorms (affine, running statistics, one float momentum), a shape vt_tactile_unet_train_supported covers."""
+        if _tactile_unet_train_mode() != "hip" or not self.training or not torch.is_grad_enabled():
+            return False
+        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32) or x.requires_grad:
+            return False
+        if x.shape[1] != self.in_channels or x.shape[0] == 0 or scenes < 1 or x.shape[0] % scenes:
+            return False
+        if not any(p.requires_grad for p in self.parameters()):
+            return False
+        bns = [blk.bn for blk in list(self.down_convs) + list(self.up_convs)]
+        m = bns[0].momentum
+        if m is None or any(not (bn.affine and bn.track_running_stats) or bn.running_mean is None or bn.momentum != m or not bn.training
+                            for bn in bns):
+            return False
+        if any(p.device != x.device or p.dtype != torch.float32 for p in self.parameters()):
+            return False
+        return ops.tactile_unet_train_supported(self, x.shape[0], x.shape[0] // scenes, x.shape[2], x.shape[3])
+
+    def forward(self, x, scenes=1):
+        """x [scenes * G, in_channels, H, W], scene-major; in train mode every BatchNorm sees each scene's G images alone."""
         if self.hip_supported(x):
             return ops.tactile_unet_fwd(x, self, self._blob())
+        if self.train_hip_supported(x, scenes):
+            return _TactileUNetTrain.apply(x, self, int(scenes), *[p for _, p in self.named_parameters()])
+        if scenes > 1:
+            G = x.shape[0] // scenes
+            return torch.cat([self.forward_modules(x[s * G:(s + 1) * G]) for s in range(scenes)], dim=0)
         return self.forward_modules(x)
+
+    def forward_scenes(self, imgs):
+        """imgs [S, F, in_channels, H, W] -> [S, F, num_classes * H * W]: the reference's loop ``cat([self(imgs[s]) for s])``
+        (models/__init__.py:115-136).  On the HIP train path it is ONE pass over the S * F images with per-scene statistics; otherwise
+        the loop itself over ``forward_modules`` (or the eval kernels), so values, gradients and running statistics are the loop's."""
+        S, Fn = imgs.shape[:2]
+        return self.forward(imgs.reshape(S * Fn, *imgs.shape[2:]), scenes=S).view(S, Fn, -1)
 
     def forward_modules(self, x):
         """The nn modules one by one (host PyTorch-ROCm / MIOpen): train mode, autograd, shapes the HIP path does not cover."""

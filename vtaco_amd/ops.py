@@ -2326,6 +2326,93 @@ def tactile_unet_fwd(x, net, blob, ws=None):
     return out
 
 
+# ---- the tactile depth estimator in train mode (unet2d_train.hip) --------------------------------------------------------------------
+
+def tactile_unet_train_supported(net, n_img, group, H, W):
+    return bool(_lib.load().vt_tactile_unet_train_supported(*_tactile_unet_dims(net), int(n_img), int(group), int(H), int(W)))
+
+
+class TactileUnetTrainWorkspace:
+    """The workspace of one (device, stream, shape): the forward fills it and the backward reads it.  ``gen`` counts the forwards that
+    wrote it, so a backward can tell whether its forward was the last one (layers._TactileUNetTrain runs the forward again if not)."""
+
+    def __init__(self, buf):
+        self.buf, self.gen = buf, 0
+
+
+_tactile_unet_train_ws = {}  # (device, stream, dims, images, group, H, W) -> TactileUnetTrainWorkspace; at most _RESNET_WS_MAX, oldest first
+
+
+def tactile_unet_train_workspace(net, n_img, group, H, W):
+    """Workspace of vt_tactile_unet_train_fwd / vt_tactile_unet_bwd, one per (device, STREAM, shape), like tactile_unet_workspace."""
+    lib = _lib.load()
+    dev = torch.cuda.current_device()
+    key = (dev, torch.cuda.current_stream().cuda_stream, _tactile_unet_dims(net), int(n_img), int(group), int(H), int(W))
+    ws = _tactile_unet_train_ws.get(key)
+    if ws is None:
+        n = lib.vt_tactile_unet_train_workspace_bytes(*_tactile_unet_dims(net), int(n_img), int(group), int(H), int(W))
+        if n == 0:
+            raise VtError("tactile U-Net train shape not built (vt_tactile_unet_train_supported)")
+        ws = TactileUnetTrainWorkspace(torch.empty(n, dtype=torch.uint8, device=torch.device("cuda", dev)))
+        while len(_tactile_unet_train_ws) >= _RESNET_WS_MAX:
+            _tactile_unet_train_ws.pop(next(iter(_tactile_unet_train_ws)))
+        _tactile_unet_train_ws[key] = ws
+    return ws
+
+
+def tactile_unet_train_fwd(x, net, scenes=1, momentum=None, ws=None):
+    """TactileUNet.forward in train mode on the HIP kernels (vt_tactile_unet_train_fwd): x [scenes * G, in_channels, H, W], scene-major,
+    every BatchNorm with the statistics of each scene's G images alone -> [scenes * G, num_classes, H, W].  ``momentum`` (a float):
+    the blocks' running_mean / running_var are updated in place as ``scenes`` sequential calls would; None leaves them alone
+    (num_batches_tracked is the caller's).  ``ws`` (tactile_unet_train_workspace) keeps what tactile_unet_bwd reads."""
+    x = _c(x)
+    if x.dim() != 4 or x.shape[1] != net.in_channels or x.shape[0] % int(scenes):
+        raise VtError(f"tactile_unet_train_fwd: input must be [scenes * G, {net.in_channels}, H, W] (got {tuple(x.shape)}, scenes {scenes})")
+    n_img, _, H, W = x.shape
+    group = n_img // int(scenes)
+    if ws is None:
+        ws = tactile_unet_train_workspace(net, n_img, group, H, W)
+    prm, keep = tactile_unet_params(net)
+    out = torch.empty((n_img, prm.num_classes, H, W), dtype=torch.float32, device=x.device)
+    check(_lib.load().vt_tactile_unet_train_fwd(dev_ptr(x, "x"), n_img, group, H, W, ctypes.byref(prm), -1.0 if momentum is None else float(momentum),
+                                                ctypes.c_void_p(ws.buf.data_ptr()), ws.buf.numel(), dev_ptr(out, "out"), stream_ptr()),
+          "vt_tactile_unet_train_fwd")
+    ws.gen += 1
+    return out
+
+
+def tactile_unet_bwd(dout, out, net, scenes, ws):
+    """Backward of tactile_unet_train_fwd (vt_tactile_unet_bwd): {parameter name: gradient} for every parameter of the net from dout, the
+    forward's output and the workspace it filled.  Gradients are written, not accumulated; a block's bn.weight / bn.bias gradient is
+    the sum over its two uses."""
+    dout, out = _c(dout), _c(out)
+    n_img, _, H, W = out.shape
+    prm, keep = tactile_unet_params(net)
+    g = _lib.TactileUnetGrads()
+    grads = {}
+
+    def buf(name, like):
+        t = torch.empty(like.shape, dtype=torch.float32, device=out.device)
+        grads[name] = t
+        return dev_ptr(t, name).value
+
+    def pair(w, b, bw, bb, i, blk, name):
+        for k, cname in enumerate(("conv1", "conv2")):
+            conv = getattr(blk, cname)
+            w[i][k], b[i][k] = buf(f"{name}.{cname}.weight", conv.weight), buf(f"{name}.{cname}.bias", conv.bias)
+        bw[i], bb[i] = buf(name + ".bn.weight", blk.bn.weight), buf(name + ".bn.bias", blk.bn.bias)
+    for i, blk in enumerate(net.down_convs):
+        pair(g.down_w, g.down_b, g.down_bn_w, g.down_bn_b, i, blk, f"down_convs.{i}")
+    for j, blk in enumerate(net.up_convs):
+        i = prm.depth - 2 - j                                         # the level this block produces
+        pair(g.up_w, g.up_b, g.up_bn_w, g.up_bn_b, i, blk, f"up_convs.{j}")
+        g.up_tw[i], g.up_tb[i] = buf(f"up_convs.{j}.upconv.weight", blk.upconv.weight), buf(f"up_convs.{j}.upconv.bias", blk.upconv.bias)
+    g.final_w, g.final_b = buf("conv_final.weight", net.conv_final.weight), buf("conv_final.bias", net.conv_final.bias)
+    check(_lib.load().vt_tactile_unet_bwd(dev_ptr(dout, "dout"), dev_ptr(out, "out"), n_img, n_img // int(scenes), H, W, ctypes.byref(prm),
+                                          ctypes.c_void_p(ws.buf.data_ptr()), ws.buf.numel(), ctypes.byref(g), stream_ptr()), "vt_tactile_unet_bwd")
+    return grads
+
+
 def depth_cloud(pred, pose, width, height, fov=60.0, dtype=torch.float64):
     """Every pixel of the predicted depth images as a point of the object's normalised frame (vt_depth_cloud): pred [n_images, H*W] f32
     (the depth estimator's output), pose [n_images, 16] f64 (inverse pose 3 x 3, translation, cloud centroid, scale: the records of
