@@ -32,7 +32,7 @@ import importlib
 for name, pp, sv in (("uniform", p, save), ("clustered", p2, save2)):
     outs = {}
     for mode in (True, False):
-        ops.GRID_SCATTER_SORTED = mode
+        ops.decode_train.GRID_SCATTER_SORTED = mode
         outs[mode] = ops.decode_bwd(tuple(grid.shape), bt, go, sv, pts=pp, want_grid_grad=True)[0]
         print(name, "sorted" if mode else "per point", timed(lambda: ops.decode_bwd(tuple(grid.shape), bt, go, sv, pts=pp, want_grid_grad=True)), "ms")
     d = (outs[True] - outs[False]).abs().max().item(); m = outs[False].abs().max().item()

@@ -16,36 +16,33 @@ from torch.nn import functional as F
 
 from . import ops
 
-# the eval-mode forward of TactileResNet: "hip" = vt_resnet_fwd (csrc/resnet2d.hip), "host" = the nn modules (MIOpen)
-# (read at every call, so a tool can time both paths in one process)
-def _tactile_resnet_mode():
-    mode = os.environ.get("VTACO_TACTILE_RESNET", "hip")
-    if mode not in ("hip", "host"):
-        raise ValueError(f"VTACO_TACTILE_RESNET must be 'hip' or 'host' (got {mode!r})")
-    return mode
-
-
-# the eval-mode forward of TactileUNet: "hip" = vt_tactile_unet_fwd (csrc/unet2d.hip), "host" = the nn modules (MIOpen); read at every call
+# Which path a tactile net's forward takes: "hip" = the HIP kernels, "host" = the nn modules (MIOpen).  One environment variable per path,
+# read at every call, so a tool can time both paths in one process:
+#   VTACO_TACTILE_RESNET      the eval-mode forward of TactileResNet (vt_resnet_fwd, csrc/resnet2d.hip); default "hip"
+#   VTACO_TACTILE_UNET        the eval-mode forward of TactileUNet (vt_tactile_unet_fwd, csrc/unet2d.hip)
+#   VTACO_TACTILE_UNET_TRAIN  its train-mode forward and backward under autograd (vt_tactile_unet_train_fwd / vt_tactile_unet_bwd,
+#                             csrc/unet2d_train.hip)
 _TACTILE_UNET_DEFAULT = "hip"
-
-
-def _tactile_unet_mode():
-    mode = os.environ.get("VTACO_TACTILE_UNET", _TACTILE_UNET_DEFAULT)
-    if mode not in ("hip", "host"):
-        raise ValueError(f"VTACO_TACTILE_UNET must be 'hip' or 'host' (got {mode!r})")
-    return mode
-
-
-# the train-mode forward and backward of TactileUNet under autograd: "hip" = vt_tactile_unet_train_fwd / vt_tactile_unet_bwd
-# (csrc/unet2d_train.hip), "host" = the nn modules (MIOpen); read at every call
 _TACTILE_UNET_TRAIN_DEFAULT = "host"
 
 
-def _tactile_unet_train_mode():
-    mode = os.environ.get("VTACO_TACTILE_UNET_TRAIN", _TACTILE_UNET_TRAIN_DEFAULT)
+def _kernel_mode(variable, default):
+    mode = os.environ.get(variable, default)
     if mode not in ("hip", "host"):
-        raise ValueError(f"VTACO_TACTILE_UNET_TRAIN must be 'hip' or 'host' (got {mode!r})")
+        raise ValueError(f"{variable} must be 'hip' or 'host' (got {mode!r})")
     return mode
+
+
+def _tactile_resnet_mode():
+    return _kernel_mode("VTACO_TACTILE_RESNET", "hip")
+
+
+def _tactile_unet_mode():
+    return _kernel_mode("VTACO_TACTILE_UNET", _TACTILE_UNET_DEFAULT)
+
+
+def _tactile_unet_train_mode():
+    return _kernel_mode("VTACO_TACTILE_UNET_TRAIN", _TACTILE_UNET_TRAIN_DEFAULT)
 
 
 class _TactileUNetTrain(torch.autograd.Function):

@@ -1,0 +1,29 @@
+"""Host-side launchers for the HIP kernels behind the C ABI (include/vtaco_hip.h), one module per kernel family.
+
+Thin and allocation-explicit: every function takes torch HIP tensors, hands raw
+device pointers + the current stream to libvtaco_hip.so and returns torch
+tensors.  No function here computes anything with torch ops.
+
+This file only re-exports: callers write ``ops.name`` and look the name up at call time.  A switch that is assigned at run time
+(``decode_train.GRID_SCATTER_SORTED``, ``unet3d._WGRAD_UP``) is read by its own module: assign it there, not to the copy here.
+"""
+from . import (_base, decode, decode_train, decode_wide, fusion, labels, mano, mc, metrics, mise, nets2d, pointnet, touch, unet3d,  # noqa: F401
+               voxel)
+from ._base import *            # noqa: F401,F403
+from ._base import _c, _lib, _ptr_array     # noqa: F401
+from .decode import *           # noqa: F401,F403
+from .decode import _cl_storage             # noqa: F401
+from .decode_train import *     # noqa: F401,F403
+from .decode_wide import *      # noqa: F401,F403
+from .fusion import *           # noqa: F401,F403
+from .labels import *           # noqa: F401,F403
+from .mano import *             # noqa: F401,F403
+from .mc import *               # noqa: F401,F403
+from .mc import _mc_guess                   # noqa: F401
+from .metrics import *          # noqa: F401,F403
+from .mise import *             # noqa: F401,F403
+from .nets2d import *           # noqa: F401,F403
+from .pointnet import *         # noqa: F401,F403
+from .touch import *            # noqa: F401,F403
+from .unet3d import *           # noqa: F401,F403
+from .voxel import *            # noqa: F401,F403
