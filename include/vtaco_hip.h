@@ -1058,6 +1058,52 @@ int vt_resnet_fwd(const float *x, int n_img, int H, int W, const vt_resnet_param
                   void *workspace, size_t workspace_bytes, float *out, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Tactile feature encoder, train mode: forward with batch statistics and the      */
+/*   backward for every parameter (resnet2d_train.hip).  Replaces ResNet.forward   */
+/*   with BasicBlocks in train mode under autograd (src/layers.py:54-207) as        */
+/*   ConvolutionalOccupancyNetwork.encode_img_inputs calls it once per scene        */
+/*   (src/conv_onet/models/__init__.py:115-136).                                    */
+/* x [n_img][3][H][W], IMAGE-major: image f of scene b is row f * scenes + b, so    */
+/*   the images n with n % scenes == b are one statistics group.  Every conv        */
+/*   (no bias) writes its raw output z; per (scene, channel) the mean and biased    */
+/*   variance of z; gamma (z - mean) / sqrt(var + eps) + beta fused with the ReLU   */
+/*   (and the 3x3/2 max-pool after the stem, the residual after bn2).  The raw      */
+/*   weights of params_host are packed at every call; no blob.  momentum >= 0:      */
+/*   the running_mean / running_var the params point to are UPDATED in place, per   */
+/*   BatchNorm scene after scene: running = (1 - m) running + m batch (unbiased     */
+/*   variance); momentum < 0 leaves them alone.  num_batches_tracked (+ scenes per  */
+/*   BatchNorm) is the caller's.  out [n_img][num_classes].                         */
+/* vt_resnet_bwd: from dout [n_img][num_classes], x and the workspace the forward   */
+/*   filled (same shape, same params), the gradient of every parameter              */
+/*   (vt_resnet_grads: written, not accumulated).  No gradient for x.               */
+/* Exact-f32 matrix core for the convs, their data and weight gradients; the        */
+/*   per-channel sums and the weight gradients' partials are combined in f64 in a   */
+/*   fixed order that is a function of the layer and of one scene's images alone:   */
+/*   no atomics, bit-reproducible, a scene's outputs do not depend on the others.   */
+/* Covered (vt_resnet_train_supported): what vt_resnet_supported covers with        */
+/*   scenes >= 1 dividing n_img, n_img * ceil(H / 2) * ceil(W / 2) * 64 < 2^31 and   */
+/*   at least 2 values per scene and channel at layer4.  Unsupported: the size      */
+/*   query returns 0.  The workspace keeps every conv's z and activation, the       */
+/*   packed weights, four gradient buffers and the partials (the list:              */
+/*   rt_workspace in resnet2d_train.hip, restated in tests/resnet_train_util.py).   */
+/* ------------------------------------------------------------------------- */
+typedef struct vt_resnet_block_grads {
+    float *conv1_w, *bn1_w, *bn1_b, *conv2_w, *bn2_w, *bn2_b;
+    float *down_w, *down_bn_w, *down_bn_b;     /* first block of layer2..4, else unused */
+} vt_resnet_block_grads;
+typedef struct vt_resnet_grads {
+    float *conv1_w, *bn1_w, *bn1_b;
+    vt_resnet_block_grads block[4][VT_RESNET_MAX_BLOCKS];
+    float *linear_w, *linear_b, *fc_w, *fc_b;
+} vt_resnet_grads;
+int vt_resnet_train_supported(const int32_t *blocks_num, int num_classes, int n_img, int scenes, int H, int W);
+size_t vt_resnet_train_workspace_bytes(const int32_t *blocks_num, int num_classes, int n_img, int scenes, int H, int W);
+int vt_resnet_train_fwd(const float *x, int n_img, int scenes, int H, int W, const vt_resnet_params *params_host, double momentum,
+                        void *workspace, size_t workspace_bytes, float *out, void *stream);
+int vt_resnet_bwd(const float *dout, const float *x, int n_img, int scenes, int H, int W, const vt_resnet_params *params_host,
+                  void *workspace, size_t workspace_bytes, const vt_resnet_grads *grads_host, void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* Tactile depth estimator, eval mode (unet2d.hip).  Replaces UNet.forward        */
 /*   (src/layers.py:322-450; up_mode 'transpose', merge_mode 'concat': `depth`     */
 /*   DownConvs, depth - 1 UpConvs, conv_final, sigmoid) as                         */

@@ -116,6 +116,18 @@ class ResnetParams(ctypes.Structure):
                 ("linear_w", ctypes.c_void_p), ("linear_b", ctypes.c_void_p), ("fc_w", ctypes.c_void_p), ("fc_b", ctypes.c_void_p)]
 
 
+class ResnetBlockGrads(ctypes.Structure):
+    """Mirror of ``vt_resnet_block_grads``."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("conv1_w", "bn1_w", "bn1_b", "conv2_w", "bn2_w", "bn2_b", "down_w", "down_bn_w", "down_bn_b")]
+
+
+class ResnetGrads(ctypes.Structure):
+    """Mirror of ``vt_resnet_grads``."""
+    _fields_ = [("conv1_w", ctypes.c_void_p), ("bn1_w", ctypes.c_void_p), ("bn1_b", ctypes.c_void_p),
+                ("block", (ResnetBlockGrads * VT_RESNET_MAX_BLOCKS) * 4),
+                ("linear_w", ctypes.c_void_p), ("linear_b", ctypes.c_void_p), ("fc_w", ctypes.c_void_p), ("fc_b", ctypes.c_void_p)]
+
+
 VT_TACTILE_UNET_MAX_DEPTH = 5
 VT_TACTILE_UNET_MAX_CLASSES = 4
 
@@ -267,6 +279,10 @@ SIGNATURES = {
     "vt_resnet_workspace_bytes": (_SZ, [ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I]),
     "vt_resnet_pack": (_I, [ctypes.POINTER(ResnetParams), _VP, _SZ, _VP]),
     "vt_resnet_fwd": (_I, [_VP, _I, _I, _I, ctypes.POINTER(ResnetParams), _VP, _VP, _SZ, _VP, _VP]),
+    "vt_resnet_train_supported": (_I, [ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I, _I]),
+    "vt_resnet_train_workspace_bytes": (_SZ, [ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I, _I]),
+    "vt_resnet_train_fwd": (_I, [_VP, _I, _I, _I, _I, ctypes.POINTER(ResnetParams), _D, _VP, _SZ, _VP, _VP]),
+    "vt_resnet_bwd": (_I, [_VP, _VP, _I, _I, _I, _I, ctypes.POINTER(ResnetParams), _VP, _SZ, ctypes.POINTER(ResnetGrads), _VP]),
     "vt_tactile_unet_supported": (_I, [_I, _I, _I, _I, _I, _I, _I]),
     "vt_tactile_unet_blob_bytes": (_SZ, [_I, _I, _I, _I]),
     "vt_tactile_unet_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),

@@ -22,8 +22,11 @@ from . import ops
 #   VTACO_TACTILE_UNET        the eval-mode forward of TactileUNet (vt_tactile_unet_fwd, csrc/unet2d.hip)
 #   VTACO_TACTILE_UNET_TRAIN  its train-mode forward and backward under autograd (vt_tactile_unet_train_fwd / vt_tactile_unet_bwd,
 #                             csrc/unet2d_train.hip)
+#   VTACO_TACTILE_RESNET_TRAIN  the train-mode forward and backward of TactileResNet under autograd (vt_resnet_train_fwd / vt_resnet_bwd,
+#                             csrc/resnet2d_train.hip)
 _TACTILE_UNET_DEFAULT = "hip"
 _TACTILE_UNET_TRAIN_DEFAULT = "host"
+_TACTILE_RESNET_TRAIN_DEFAULT = "host"
 
 
 def _kernel_mode(variable, default):
@@ -43,6 +46,40 @@ def _tactile_unet_mode():
 
 def _tactile_unet_train_mode():
     return _kernel_mode("VTACO_TACTILE_UNET_TRAIN", _TACTILE_UNET_TRAIN_DEFAULT)
+
+
+def _tactile_resnet_train_mode():
+    return _kernel_mode("VTACO_TACTILE_RESNET_TRAIN", _TACTILE_RESNET_TRAIN_DEFAULT)
+
+
+class _TactileResNetTrain(torch.autograd.Function):
+    """TactileResNet.forward in train mode under autograd on the HIP kernels: ops.resnet_train.fwd / bwd.  ``params`` = the net's
+    parameters in named_parameters() order (autograd inputs, so the optimiser's tensors receive the gradients); x gets none.  The
+    workspace is shared per (device, stream, shape): if another forward of that shape ran before this call's backward, the backward
+    first runs the forward again (running statistics untouched)."""
+
+    @staticmethod
+    def forward(ctx, x, net, scenes, *params):
+        n_img, _, H, W = x.shape
+        ws = ops.resnet_train.workspace(net, n_img, scenes, H, W)
+        out = ops.resnet_train.fwd(x, net, scenes, momentum=float(net.bn1.momentum), ws=ws)
+        with torch.no_grad():
+            for bn in net._batchnorms():
+                bn.num_batches_tracked += scenes                     # (also moves the eval path's blob stamp: the kernel wrote the statistics)
+        ctx.net, ctx.scenes, ctx.ws, ctx.gen = net, scenes, ws, ws.gen
+        ctx.save_for_backward(x, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x = ctx.saved_tensors[0]                                     # (raises if a parameter changed since the forward)
+        net = ctx.net
+        if ctx.ws.gen != ctx.gen:
+            ops.resnet_train.fwd(x, net, ctx.scenes, momentum=None, ws=ctx.ws)
+            ctx.gen = ctx.ws.gen
+        grads = ops.resnet_train.bwd(dout, x, net, ctx.scenes, ctx.ws)
+        return (None, None, None) + tuple(grads[name] if need else None
+                                          for (name, _), need in zip(net.named_parameters(), ctx.needs_input_grad[3:]))
 
 
 class _TactileUNetTrain(torch.autograd.Function):
@@ -329,8 +366,10 @@ class TactileResNet(nn.Module):
     BasicBlocks, src/layers.py:127-195): 7x7/2 stem, 3x3/2 max-pool, four stages of residual pairs (64, 128, 256, 512; stride 2
     from the second), global average pool, Linear(512, 100), Linear(100, num_classes) -- no activation between the two.
     Five 320x240 images per scene.  In eval mode without autograd on a HIP f32 input the forward is ``vt_resnet_fwd``
-    (csrc/resnet2d.hip: BatchNorm folded into the convs, 18 launches for Resnet18, bit-reproducible); train mode, anything under
-    autograd and ``VTACO_TACTILE_RESNET=host`` run the nn modules (``forward_modules``: host PyTorch-ROCm / MIOpen)."""
+    (csrc/resnet2d.hip: BatchNorm folded into the convs, 18 launches for Resnet18, bit-reproducible).  In train mode under autograd
+    with ``VTACO_TACTILE_RESNET_TRAIN=hip`` the forward and the backward are ``vt_resnet_train_fwd`` / ``vt_resnet_bwd``
+    (csrc/resnet2d_train.hip: batch statistics per scene, every parameter's gradient, bit-reproducible; ``train_hip_supported``).
+    Everything else and ``VTACO_TACTILE_RESNET=host`` run the nn modules (``forward_modules``: host PyTorch-ROCm / MIOpen)."""
 
     def __init__(self, blocks_num=(2, 2, 2, 2), num_classes=32):
         super().__init__()
@@ -383,9 +422,42 @@ class TactileResNet(nn.Module):
             self.__dict__["_blob_cache"] = hit
         return hit[1]
 
+    def _batchnorms(self):
+        """Every BatchNorm of the net: the stem's, each block's bn1 / bn2 and each projection's."""
+        bns = [self.bn1]
+        for stage in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for blk in stage:
+                bns += [blk.bn1, blk.bn2] + ([blk.downsample[1]] if blk.downsample is not None else [])
+        return bns
+
+    def train_hip_supported(self, x, scenes=1):
+        """Train mode with autograd on, a parameter that requires grad, a HIP f32 image batch that does not, VTACO_TACTILE_RESNET_TRAIN=hip,
+        ordinary BatchNorms (affine, running statistics, one float momentum), BasicBlock stages, a shape vt_resnet_train_supported
+        covers (``scenes`` divides the batch; at least 2 values per scene and channel at layer4)."""
+        if _tactile_resnet_train_mode() != "hip" or not self.training or not torch.is_grad_enabled():
+            return False
+        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32) or x.requires_grad:
+            return False
+        if x.shape[1] != 3 or x.shape[0] == 0 or scenes < 1 or x.shape[0] % scenes:
+            return False
+        if not any(p.requires_grad for p in self.parameters()):
+            return False
+        if any(not isinstance(blk, _ResidualPair) for stage in (self.layer1, self.layer2, self.layer3, self.layer4) for blk in stage):
+            return False
+        bns = self._batchnorms()
+        m = bns[0].momentum
+        if m is None or any(type(bn) is not nn.BatchNorm2d or not (bn.affine and bn.track_running_stats) or bn.running_mean is None
+                            or bn.momentum != m or not bn.training for bn in bns):
+            return False
+        if any(p.device != x.device or p.dtype != torch.float32 for p in self.parameters()):
+            return False
+        return ops.resnet_train.supported(self, x.shape[0], scenes, x.shape[2], x.shape[3])
+
     def forward(self, x, scenes=1):
         if self.hip_supported(x):
                 return ops.resnet_fwd(x, self, self._blob())
+        if self.train_hip_supported(x, scenes):
+            return _TactileResNetTrain.apply(x, self, int(scenes), *[p for _, p in self.named_parameters()])
         return self.forward_modules(x, scenes)
 
     def forward_modules(self, x, scenes=1):
