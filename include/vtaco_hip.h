@@ -444,6 +444,20 @@ int vt_fusion_dropout_mask_wide(float p_drop, unsigned long long seed, int call,
 /*                       fc_0.w[5][..] fc_0.b[5][32] fc_1.w[5][..] fc_1.b[5][32]   */
 /*                       fc_out.w[32] fc_out.b[1]; p_in = 35 iff c_img != NULL.   */
 /*                       Partials are summed in a fixed order: bit-reproducible.  */
+/* Buffer layouts (P = B*N points, each slot P rows of 32 floats, row = point):  */
+/*   save [12][P][32], written by vt_decode_fwd / vt_decode_mlp_fwd_train:        */
+/*     slot 0       c, the sampled (or given) features                            */
+/*     slots 1..5   relu(x_i), x_i the input of block i (fc_c_i(c) included)      */
+/*     slots 6..10  relu(h_i), h_i = fc_0_i(relu(x_i))                            */
+/*     slot 11      relu(net_5), the input of both output heads                   */
+/*     (the values are the layer inputs of the weight gradients, their signs the  */
+/*      ReLU masks of the data pass)                                              */
+/*   gws [11][P][32], written by vt_decode_bwd / _dc / vt_decode_mlp_bwd, read by */
+/*   vt_decode_wgrad:                                                             */
+/*     slot 0       d x_0   (-> fc_p / fc_p_img and fc_c_0)                       */
+/*     slots 1..5   d h_i   (-> fc_0_i, with save slot 1+i)                       */
+/*     slots 6..10  d (output of block i) = d x_i+1, slot 10 = d net_5            */
+/*                  (-> fc_1_i with save slot 6+i, and fc_c_i+1 with save slot 0) */
 /* ------------------------------------------------------------------------- */
 size_t vt_decoder_blob_t_bytes(int hidden, int c_dim, int n_blocks);
 int vt_decoder_pack_t(const vt_decoder_params *params_host, float *blob_t, size_t blob_bytes, void *stream);

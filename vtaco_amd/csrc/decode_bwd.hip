@@ -207,8 +207,15 @@ sample_grid_bwd_kernel(DecodeArgs d, const float *grad_feat, float *grad_grid, i
 // in registers -- ascending point order -- and issues 8 x 32 atomics per CELL instead of per point.  Training samples are not
 // spread evenly: the contact clouds put up to 128 points of a scene within millimetres, i.e. into a handful of cells, and f32
 // atomics that collide on one address retire one after the other (decode_bwd_data_kernel's own scatter: 0.92 ms of a step's
-// 16 384 points against 0.1 ms for everything else it does).  A point whose own cell differs from its bin's (the two
-// normalisations round differently on a cell boundary) falls back to its own 8 x 32 atomics: same sum either way.
+// 16 384 points against 0.1 ms for everything else it does).
+// Contract of order / seg_lo / seg_hi: any partition of each scene's points into segments in the vt_voxel_build format (ord[seg_lo]
+// is the segment's head, every point lies in exactly one segment).  A point whose own trilinear cell differs from its head's falls
+// back to its own 8 x 32 atomics, so the sum is the same for every partition; only the number of atomics changes (checked against
+// float64 with segments from vt_voxel_build at resolution 1 and 2 under R = 5 and 8: tests/test_decode_train_f64_gpu.py).  With segments
+// from vt_voxel_build at R - 1 -- all that ops.decode_bwd and ops.sample_grid_bwd pass -- the fallback never runs: both
+// normalisations start from the same float32 q = v / divisor + 0.5, and ((2q - 1) + 1) / 2 gives q back exactly, so
+// int(q (R - 1)) IS floor(f) (probed on the CPU over 200 001 coordinates and +-200 ulps around every cell boundary for R = 3, 5, 9,
+// 17, 33: tests/test_decode_train_ref_cpu.py).  It runs only for a caller with segments of its own, e.g. a coarser binning.
 __global__ void __launch_bounds__(256)
 sample_grid_bwd_sorted_kernel(DecodeArgs d, const float *grad_feat, const int *order, const int *seg_lo, const int *seg_hi, float *grad_grid, int C) {
     const int lane = threadIdx.x & 63, ch = (lane & 31) + 32 * blockIdx.y, half = lane >> 5;         // blockIdx.y = the 32-channel slice
