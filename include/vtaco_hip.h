@@ -329,6 +329,44 @@ int vt_decode_bwd_dc(int B, int R, int C, const float *pts, int64_t N, double pa
                      float *grad_c, float *grad_c_img, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Plane features: the bilinear samples of the canonical planes (sample_planes.hip). */
+/* Replaces: sample_plane_feature and the key walk around it at decoder.py:55-60, 135-147 */
+/* (normalize_coordinate, src/common.py:268-291: divisor 1 + padding + 10e-6, values >= 1 become 1 - 10e-6, values < 0 */
+/* become 0 -- not the 3-D constants; F.grid_sample with align_corners=True and border padding).                        */
+/*   feat[B,N,C] = base? + xz? + xy? + yz?   summed in exactly that order.                                              */
+/* xz / xy / yz: [B,C,R,R] float32 contiguous, NULL = absent, at least one present; all share one square R in [2, 1024];  */
+/* C % 32 == 0, C <= 256.  The projected axes are vt_plane_build's (xz: x, z; xy: x, y; yz: y, z); the first indexes the   */
+/* last (W) dimension.  base: optional [B,N,C] to add onto (the result of vt_sample_grid: the grid is the reference's first */
+/* term), may alias feat.  Query points: pts [B,N,3], or NULL with the lattice (lattice_nx, lattice_box, lattice_first, N)  */
+/* in vt_sample_grid's arithmetic (nx <= 1625: nx^3 below 2^32).  flags: VT_PLANES_NEAREST = mode 'nearest' (half to even) instead of 'bilinear';         */
+/* VT_PLANES_LATTICE_POINTS = the lattice through the point kernel on generated coordinates instead of the per-plane tables */
+/* of the nx^2 distinct samples (the same bits either way, and the same bits as the point form on the materialised lattice). */
+/* workspace: vt_sample_planes_workspace_bytes(B, R, C, number of planes present, lattice_nx or 0) bytes, 16-byte aligned   */
+/* like base and feat.  Bad arguments return VT_ERR_INVALID / VT_ERR_UNSUPPORTED / VT_ERR_WORKSPACE before any GPU call.    */
+#define VT_PLANES_NEAREST 1
+#define VT_PLANES_LATTICE_POINTS 2
+/* VT_PLANES_PREPARED: the workspace still holds the channels-last copies (and, in table form, the tables) an earlier call left  */
+/* there for the same planes, R, C, flags and lattice nx / box: the call skips that preparation (the slabs of one lattice, the     */
+/* levels of one MISE extraction).  The caller vouches for it; a different lattice_first / N / pts / base is what may change.    */
+#define VT_PLANES_PREPARED 4
+size_t vt_sample_planes_workspace_bytes(int B, int R, int C, int n_planes, int lattice_nx);
+int vt_sample_planes(const float *xz, const float *xy, const float *yz, int B, int R, int C,
+                     const float *pts, int64_t N, int lattice_nx, float lattice_box, int64_t lattice_first,
+                     double padding, int flags, const float *base, float *feat,
+                     void *workspace, size_t workspace_bytes, void *stream);
+/* Its backward (the autograd of decoder.py:55-60): grad_feat [B,N,C] -> grad_xz / grad_xy / grad_yz [B,C,R,R] for the     */
+/* non-NULL outputs (at least one).  The outputs are WRITTEN, every element, not accumulated into: no pre-zeroed memory is  */
+/* asked of the caller; a NULL output's plane is skipped.  Bilinear: four pixels with the forward's weights; nearest: one.   */
+/* The gradient to base is grad_feat itself.  The points are grouped by bilinear cell (vt_plane_build_multi at R - 1) and    */
+/* one wave per cell sums in ascending point order before its f32 atomics, so clustered points cost one atomic set per cell. */
+/* Query points only (pts [B,N,3], not a lattice).  workspace: vt_sample_planes_bwd_workspace_bytes(B, N, R, C, number of    */
+/* outputs) bytes, 16-byte aligned.                                                                                          */
+size_t vt_sample_planes_bwd_workspace_bytes(int B, int64_t N, int R, int C, int n_planes);
+int vt_sample_planes_bwd(int B, int R, int C, const float *pts, int64_t N, double padding, int flags,
+                         const float *grad_feat, float *grad_xz, float *grad_xy, float *grad_yz,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* TransformerFusion forward (eval mode).                                       */
 /* Replaces: self.fuser(c_img, 1, c, 1) at decoder.py:258, i.e.                  */
 /*   TransformerFusion.forward (src/TransformerFusion.py:311-333) with           */

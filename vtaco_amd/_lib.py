@@ -365,6 +365,10 @@ SIGNATURES = {
     "vt_conv1x1_cl": (_I, [_VP, _I64, _I, _VP, _VP, _I, _VP, _VP]),
     "vt_voxel_scatter_mean_cl_fwd": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP]),
     "vt_voxel_scatter_mean_cl_bwd": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP]),
+    "vt_sample_planes_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "vt_sample_planes": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _I64, _I, _F, _I64, _D, _I, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_sample_planes_bwd_workspace_bytes": (_SZ, [_I, _I64, _I, _I, _I]),
+    "vt_sample_planes_bwd": (_I, [_I, _I, _I, _VP, _I64, _D, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "vt_chamfer_nn": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "vt_emd_workspace_bytes": (_SZ, [_I, _I]),
     "vt_emd_auction": (_I, [_VP, _I, _VP, _I, _I, _F, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),

@@ -270,7 +270,17 @@ class Generator3D(object):
 
     # -- fast path: the nx^3 lattice never exists as a tensor ----------------------
     def eval_lattice(self, c, nx, c_img_all=None, first=0, count=None, out=None):
-        """Logits of the (1+padding)-box lattice, device tensor [count] (whole: nx^3)."""
+        """Logits of the (1+padding)-box lattice, device tensor [count] (whole: nx^3).  ``out``: a contiguous float32 tensor of
+        ``count`` elements to write them into."""
+        if isinstance(c, dict) and set(c) != {'grid'}:
+            # plane features (alone or next to the volume): the decoder's sampled route, slab by slab (LocalDecoder.decode_lattice)
+            one = next(iter(c.values()))
+            if one.shape[0] != 1:
+                raise VtError("eval_lattice: one scene at a time (the lattice is per scene)")
+            if count == 0:
+                return torch.empty(0, dtype=torch.float32, device=one.device)
+            return self.model.decoder.decode_lattice(c, nx, box=1 + self.padding, first=first, count=count, c_img=c_img_all, out=out,
+                                                     precision=self.decode_precision).reshape(-1)
         grid = c['grid'] if isinstance(c, dict) else c
         if grid.shape[0] != 1:
             raise VtError("eval_lattice: one scene at a time (the lattice is per scene)")
@@ -278,6 +288,16 @@ class Generator3D(object):
             return torch.empty(0, dtype=torch.float32, device=grid.device)
         return self.model.decoder.decode_lattice(grid, nx, box=1 + self.padding, first=first, count=count,
                                                  c_img=c_img_all, out=out, precision=self.decode_precision).reshape(-1)
+
+    def _plane_model(self):
+        """True if the model's encoder returns canonical planes ('xz','xy','yz') instead of the feature volume."""
+        enc = getattr(self.model, "encoder", None)
+        return enc is not None and getattr(enc, "planes", ['grid']) != ['grid']
+
+    def _refuse_planes(self, what, why):
+        if self._plane_model():
+            raise VtError(f"Generator3D.{what}: the encoder returns plane features {self.model.encoder.planes}, which this route does "
+                          f"not take ({why}); generate_obj_mesh_wnf without with_img and eval_lattice decode them")
 
     def extract_mesh(self, value_grid, level=None):
         """``measure.marching_cubes(value_grid, gradient_direction='ascent')`` followed by
@@ -438,6 +458,7 @@ class Generator3D(object):
         (launch-bound otherwise); only the data-dependent output sizing leaves the graph.  Safe across weight
         updates and interleaved eager calls of other shapes (see ``_scene_graph``).  Dense extraction only."""
         self._refuse_mise("generate_mesh_graphed")
+        self._refuse_planes("generate_mesh_graphed", "the captured scene graph holds the fused volume decode, vt_decode_fwd*")
         self._eval_mode()
         nx = self.resolution0 * 4
         g = self._scene_graph(inputs.shape, nx)
@@ -457,6 +478,7 @@ class Generator3D(object):
         Dense extraction only."""
         from .. import dist as vdist
         self._refuse_mise("generate_obj_mesh_sharded")
+        self._refuse_planes("generate_obj_mesh_sharded", "its slabs are aligned for the fused volume decode, vt_decode_fwd*")
         self._eval_mode()
         nx = self.resolution0 * 4
         inputs = data.get('inputs').to(self.device)
@@ -713,9 +735,11 @@ class Generator3D(object):
             return self._generate_mise(data, c_img_all)
         nx = self.resolution0 * 4                       # generation.py:120
         inputs = data.get('inputs').to(self.device)
+        if self.with_img:
+            self._refuse_planes("generate_obj_mesh_wnf(with_img)", "the tactile decodes (fc_p_img, finger ids) sample a volume")
         if self.with_img and c_img_all is None:
             return self._generate_tactile(data)
-        if (not self.with_img and self._graphs_allowed() and inputs.dim() == 3 and inputs.shape[0] == 1
+        if (not self.with_img and not self._plane_model() and self._graphs_allowed() and inputs.dim() == 3 and inputs.shape[0] == 1
                 and self._worth_capturing((tuple(inputs.shape), nx, self.decode_precision))):
             # the visual branch: the same launches replayed as one hipGraph per (cloud shape, lattice) -- 1.1 instead of 1.5 ms
             return self.generate_mesh_graphed(inputs)
@@ -771,6 +795,8 @@ class Generator3D(object):
         """(c, setup) of a tactile scene: the shape encoder's output and the branch's finger features, anchors and rule, with the
         encoders overlapped on the side streams (see _generate_tactile)."""
         self._eval_mode()
+        self._refuse_planes("generate_obj_mesh_wnf(with_img)", "the tactile decodes read the finger features in vt_decode_fwd_ids / "
+                            "the fuser's id kernels, which sample a volume")
         inputs = data.get('inputs').to(self.device)
         if inputs.shape[0] != 1:
             raise VtError(f"generate_obj_mesh_wnf: one scene at a time (got a batch of {inputs.shape[0]})")
@@ -809,8 +835,19 @@ class Generator3D(object):
         ``_mise_precision()``; with a tactile ``setup`` every point first gets its finger id (vt_tactile_assign at the points) and
         the decoder reads the finger's feature by id."""
         dec = self.model.decoder
-        grid = dec._grid_of(c) if isinstance(c, dict) else c
         prec = self._mise_precision()
+        if isinstance(c, dict) and set(c) != {'grid'}:
+            # plane features: the point path of the decoder's sampled route (vt_sample_planes, then the MLP on given features)
+            if setup is not None:
+                raise VtError("Generator3D.mise_evaluator: plane features with a tactile setup are not built (vt_decode_fwd_ids samples a volume)")
+            vol, planes = dec._features_of(c)
+            prepared = ops.planes.Prepared()            # the planes are laid out by the first level's call and kept for the others
+
+            def evaluate_planes(ids, pts):
+                p = pts.reshape(1, -1, 3)
+                return dec._mlp_given(dec._sample(p, vol, planes, prepared=prepared), p, precision=prec).reshape(-1)
+            return evaluate_planes
+        grid = dec._grid_of(c) if isinstance(c, dict) else c
         if setup is None:
             def evaluate(ids, pts):
                 p = pts.reshape(1, -1, 3)

@@ -131,6 +131,10 @@ class Inferencer(object):
         if getattr(self.generator, "extraction", "dense") != "dense":
             raise VtError("Inferencer: the session keeps the dense nx^3 lattice; the generator has extraction='mise' "
                           "(use a generator with extraction='dense')")
+        enc = getattr(self.model, "encoder", None)
+        if enc is not None and getattr(enc, "planes", ['grid']) != ['grid']:
+            raise VtError(f"Inferencer: the encoder returns plane features {enc.planes}; the session's incremental decodes read the finger "
+                          "features in vt_decode_fwd_ids, which samples the 'grid' volume only")
 
     def _check_route(self, group):
         if not self.with_img:

@@ -120,6 +120,24 @@ class _SampleGridFn(torch.autograd.Function):
         return ops.sample_grid_bwd(ctx.shape, ctx.p, grad_feat, ctx.padding), None, None
 
 
+class _SamplePlanesFn(torch.autograd.Function):
+    """The canonical planes' samples added onto ``base`` (vt_sample_planes / vt_sample_planes_bwd), differentiable in every plane and
+    in ``base`` (whose gradient is the output's).  ``keys``: the planes' names, in the order the tensors follow."""
+
+    @staticmethod
+    def forward(ctx, p, padding, nearest, base, keys, *planes):
+        ctx.keys, ctx.shape, ctx.p, ctx.padding, ctx.nearest = keys, tuple(planes[0].shape), p.detach(), padding, nearest
+        ctx.has_base = base is not None
+        # (the planes are summed onto a copy: the grid's sample stays what its own autograd node returned)
+        return ops.planes.sample_planes(dict(zip(keys, planes)), p, padding, base=None if base is None else base.detach().clone(),
+                                        nearest=nearest)
+
+    @staticmethod
+    def backward(ctx, grad_feat):
+        grads = ops.planes.sample_planes_bwd(ctx.keys, ctx.shape, ctx.p, grad_feat, ctx.padding, ctx.nearest)
+        return (None, None, None, grad_feat if ctx.has_base else None, None, *[grads[k] for k in ctx.keys])
+
+
 class _DecodeMlpFn(torch.autograd.Function):
     """The conditioned MLP on given features (vt_decode_mlp_fwd_train; backward vt_decode_mlp_bwd +
     vt_decode_wgrad): gradients to the features and to every decoder parameter (fc_p form)."""
@@ -162,7 +180,7 @@ class _DecodeMlpWideFn(torch.autograd.Function):
 
 
 class LocalDecoder(nn.Module):
-    """Decoder conditioned on a local 3-D feature grid.
+    """Decoder conditioned on a local 3-D feature grid and / or the canonical feature planes ('xz', 'xy', 'yz').
 
     Args mirror the reference (decoder.py:23-24): dim, c_dim, hidden_size,
     n_blocks, leaky, sample_mode, padding, with_contact.
@@ -274,16 +292,82 @@ class LocalDecoder(nn.Module):
                               wide=(self.hidden_size, self.n_blocks, self.leaky, self.sample_mode == 'nearest'), **kw)
 
     @staticmethod
-    def _grid_of(c_plane):
+    def _grid_of(c_plane, what="this route"):
+        """The feature volume of a grid-only ``c_plane``: the resolver of the routes whose kernels take nothing else."""
         if set(c_plane.keys()) != {'grid'}:
-            raise VtError("LocalDecoder: only the 'grid' feature volume is built (plane features belong to "
-                          "the hand branch, out of scope: SURVEY.md section 2 row 10)")
+            raise VtError(f"LocalDecoder: {what} takes the 'grid' feature volume alone (got {sorted(c_plane.keys())}): the fused "
+                          "decode kernels (vt_decode_fwd*) sample a volume; plane features ('xz','xy','yz') are decoded by "
+                          "forward, AttentionDecoder.forward_img and decode_lattice through vt_sample_planes")
         return c_plane['grid']
+
+    @staticmethod
+    def _features_of(c_plane):
+        """(grid or None, {plane: tensor}) of any non-empty subset of 'grid','xz','xy','yz' (decoder.py:137-146)."""
+        keys = set(c_plane.keys())
+        if not keys or not keys <= {'grid', 'xz', 'xy', 'yz'}:
+            raise VtError(f"LocalDecoder: c_plane must hold a non-empty subset of 'grid','xz','xy','yz' (got {sorted(keys)})")
+        return c_plane.get('grid'), {k: c_plane[k] for k in ('xz', 'xy', 'yz') if k in c_plane}
+
+    def _refuse_planes(self, c_plane, what, kernel):
+        if set(c_plane.keys()) != {'grid'}:
+            raise VtError(f"LocalDecoder.{what} with plane features {sorted(c_plane.keys())} is not built: {kernel}")
+
+    # -- the route through sampled features: grid and / or planes -> c [B,N,C] -> the conditioned MLP on given features -------------
+    def _check_nearest_grid(self, grid):
+        if grid is not None and self.sample_mode == 'nearest':
+            raise VtError("LocalDecoder: 'grid' mixed with planes under sample_mode='nearest' is not built (vt_sample_grid has no "
+                          "'nearest' form)")
+
+    def _sample(self, p, grid, planes, lattice=None, prepared=None):
+        """c = grid? + xz? + xy? + yz? at the points (or the lattice slab), no autograd: ops.sample_grid, then ops.planes.sample_planes.
+        ``prepared``: an ops.planes.Prepared the caller keeps over the calls of one scene (the planes are laid out once)."""
+        if not planes:
+            return ops.sample_grid(grid, p, self.padding, lattice=lattice)
+        self._check_nearest_grid(grid)
+        base = ops.sample_grid(grid, p, self.padding, lattice=lattice) if grid is not None else None
+        return ops.planes.sample_planes(planes, p, self.padding, base=base, lattice=lattice, nearest=self.sample_mode == 'nearest',
+                                        prepared=prepared)
+
+    def _sample_train(self, p, grid, planes):
+        """The same under autograd: _SampleGridFn, then _SamplePlanesFn (HIP forward and backward, differentiable in every source)."""
+        base = _SampleGridFn.apply(grid, p, self.padding) if grid is not None else None
+        if not planes:
+            return base
+        self._check_nearest_grid(grid)
+        keys = tuple(planes)
+        return _SamplePlanesFn.apply(p, self.padding, self.sample_mode == 'nearest', base, keys, *[planes[k].float() for k in keys])
+
+    def _mlp_given(self, c, p, precision=None, lattice=None, out=None):
+        """The conditioned MLP on given features, no autograd, in the arithmetic the grid path takes for ``precision`` (default: the
+        decoder's point precision): the split-f16 kernels for the half-precision settings, the exact-f32 ones otherwise (those
+        kernels have no split-bf16 form); the wide kernels at widths beyond 32 / 32 and with `leaky`.  ``lattice``: a slab
+        (nx, box, first, count) instead of points."""
+        prec = precision or self._point_precision()
+        if self._wide:
+            mp, wide = self._wide_precision(prec), (self.hidden_size, self.n_blocks, self.leaky)
+        else:
+            mp, wide = ("f16x3" if prec in ("f16x3", "f16f8") else "f32"), None
+        blob = self._blob(precision=mp)
+        if lattice is not None:
+            return ops.planes.decode_mlp_lattice(c, blob, lattice, precision=mp, wide=wide, out=out)
+        return ops.decode_mlp_fwd(c, blob, p, precision=mp, wide=wide)
+
+    def _forward_planes(self, p, grid, planes):
+        if not next(iter(planes.values())).is_cuda:
+            raise VtError(f"LocalDecoder: inputs must live on a HIP device (got {next(iter(planes.values())).device})")
+        feats = ([grid] if grid is not None else []) + list(planes.values())
+        if torch.is_grad_enabled() and (any(t.requires_grad for t in feats) or any(q.requires_grad for q in self.parameters())):
+            p = p.float()
+            c = self._sample_train(p, grid, planes)
+            return (_DecodeMlpWideFn if self._wide else _DecodeMlpFn).apply(self, p, c, *self._params(False))
+        return self._mlp_given(self._sample(p, grid, planes), p)
 
     # -- reference call signatures ---------------------------------------------
     def forward(self, p, c_plane, **kwargs):
         """logits [B,N] for points p [B,N,3] (decoder.py:135-161)."""
-        grid = self._grid_of(c_plane)
+        grid, planes = self._features_of(c_plane)
+        if planes:
+            return self._forward_planes(p, grid, planes)
         if self._wants_grad(grid):
             return self._wide_train(p, grid) if self._wide else _DecodeFn.apply(self, p, grid, None, *self._params(False))
         if self._wide:
@@ -293,6 +377,8 @@ class LocalDecoder(nn.Module):
 
     def forward_img(self, p, c_plane, c_img, **kwargs):
         """Tactile concat variant (decoder.py:71-103): fc_p_img([p; c_img])."""
+        self._refuse_planes(c_plane, "forward_img", "the MLP-on-given-features kernels (vt_decode_mlp_fwd*) take no c_img column "
+                            "block (fc_p_img), and the fused vt_decode_fwd* sample a volume only")
         grid = self._grid_of(c_plane)
         if self._wants_grad(grid, c_img):
             return self._wide_train(p, grid, c_img) if self._wide else _DecodeFn.apply(self, p, grid, c_img, *self._params(True))
@@ -303,6 +389,8 @@ class LocalDecoder(nn.Module):
 
     def forward_contact(self, p, c_plane, **kwargs):
         """(occupancy logits, contact logits) (decoder.py:105-133)."""
+        self._refuse_planes(c_plane, "forward_contact", "the MLP-on-given-features kernels (vt_decode_mlp_fwd*) have no second head "
+                            "(fc_out_contact), and the fused vt_decode_fwd* sample a volume only")
         grid = self._grid_of(c_plane)
         if self._wants_grad(grid) and self._wide:
             return self._wide_train(p, grid, contact=True)
@@ -319,8 +407,14 @@ class LocalDecoder(nn.Module):
     # -- dense fast path: the lattice is generated in-kernel ---------------------
     def decode_lattice(self, grid, nx, box=1.1, first=0, count=None, c_img=None, out=None, precision=None):
         """Logits of ``box * make_3d_grid((-.5,)*3,(.5,)*3,(nx,)*3)[first:first+count]``
-        (generation.py:155-157 + eval_points) without materialising the points."""
+        (generation.py:155-157 + eval_points) without materialising the points.  ``grid``: the feature volume, or a ``c_plane`` dict
+        (any non-empty subset of 'grid','xz','xy','yz').  Returns [B,count]; ``out``: a contiguous tensor of B * count floats to write
+        into ([B,count], or [count] for one scene)."""
         count = nx ** 3 - first if count is None else count
+        if isinstance(grid, dict):                 # a c_plane dict: the volume alone takes the path below, planes the sampled route
+            grid, planes = self._features_of(grid)
+            if planes:
+                return self._decode_lattice_planes(grid, planes, nx, box, first, count, c_img, out, precision)
         if self._wide:
             return self._wide_fwd(grid, precision=precision or self.precision, lattice=(nx, box, first, count), out=out,
                                   **({} if c_img is None else {"c_img": c_img.float()}))
@@ -331,10 +425,50 @@ class LocalDecoder(nn.Module):
                               padding=self.padding, lattice=(nx, box, first, count), out=out, precision=precision)
 
 
+LATTICE_SLAB_POINTS = 1 << 20       # lattice points per slab of the plane route: the feature tensor stays at 2^20 x C floats (134 MB at C = 32)
+
+
+def _decode_lattice_planes(self, grid, planes, nx, box, first, count, c_img=None, out=None, precision=None):
+    """decode_lattice with plane features: per slab of LATTICE_SLAB_POINTS points the lattice sampler (vt_sample_grid for the volume,
+    then vt_sample_planes) and the conditioned MLP on the slab's features (ops.planes.decode_mlp_lattice) -- no point tensor.
+    "f16f8" runs as "f16x3" here, as on the point path."""
+    if c_img is not None:
+        raise VtError("LocalDecoder.decode_lattice with plane features and c_img is not built: the MLP-on-given-features kernels "
+                      "(vt_decode_mlp_fwd*) take no c_img column block (fc_p_img)")
+    precision = precision or self.precision
+    if precision == "f16f8":
+        precision = "f16x3"
+    B = next(iter(planes.values())).shape[0]
+    if out is None:
+        out = torch.empty((B, count), dtype=torch.float32, device=next(iter(planes.values())).device)
+    elif out.numel() != B * count or not out.is_contiguous():
+        raise VtError(f"LocalDecoder.decode_lattice: out must be a contiguous [B,count]=({B},{count}) tensor ([count] for one scene), "
+                      f"got {tuple(out.shape)}")
+    out = out.view(B, count)
+    step = max(1, LATTICE_SLAB_POINTS // B)
+    prepared = ops.planes.Prepared()             # the planes' layout and tables are made by the first slab and kept for the others
+    for lo in range(0, count, step):
+        n = min(step, count - lo)
+        lat = (nx, box, first + lo, n)
+        c = self._sample(None, grid, planes, lattice=lat, prepared=prepared)
+        if B == 1 or n == count:
+            self._mlp_given(c, None, precision, lattice=lat, out=out[:, lo:lo + n])
+        else:
+            out[:, lo:lo + n] = self._mlp_given(c, None, precision, lattice=lat)
+    return out
+
+
+LocalDecoder._decode_lattice_planes = _decode_lattice_planes
+
+
 def _decode_lattice_ids(self, grid, nx, finger_ids, finger_feats, box=1.1, first=0, count=None, out=None, precision=None):
     """``decode_lattice`` with the tactile feature given as (finger id per point, [F,c_dim] table)
     instead of a dense c_img tensor (what the 256^3 configuration needs: 16.7 MB of ids instead of
     2.1 GB of c_img_all)."""
+    if isinstance(grid, dict):
+        self._refuse_planes(grid, "decode_lattice_ids", "the finger-id kernels (vt_decode_fwd_ids, vt_decode_fwd_wide*_ids) sample a "
+                            "volume only, and the MLP-on-given-features kernels take no tactile feature")
+        grid = grid['grid']
     count = nx ** 3 - first if count is None else count
     if self._wide:
         # the wide kernels read the ids themselves (vt_decode_fwd_wide[_f16x3]_ids): no dense [B, count, c_dim] tensor
@@ -370,15 +504,16 @@ class AttentionDecoder(LocalDecoder):
         # the reference registers fuser before fc_out_contact; order is irrelevant for load_state_dict
 
     def forward_img(self, p, c_plane, c_img, **kwargs):
-        grid = self._grid_of(c_plane)
-        if self._wants_grad(grid, c_img):
-            # under autograd every stage is HIP, forward and backward: vt_sample_grid[_bwd], vt_fusion_fwd_train / vt_fusion_bwd
-            # (train-mode dropout replayed from a seed), vt_decode_mlp_fwd_train / vt_decode_mlp_bwd / vt_decode_wgrad -- at the
+        grid, planes = self._features_of(c_plane)
+        feats = ([grid] if grid is not None else []) + list(planes.values())
+        if self._wants_grad(feats[0], c_img) or (torch.is_grad_enabled() and any(t.requires_grad for t in feats)):
+            # under autograd every stage is HIP, forward and backward: vt_sample_grid[_bwd] and vt_sample_planes[_bwd], vt_fusion_fwd_train /
+            # vt_fusion_bwd (train-mode dropout replayed from a seed), vt_decode_mlp_fwd_train / vt_decode_mlp_bwd / vt_decode_wgrad -- at the
             # widths beyond 32 / 32 vt_decode_mlp_fwd_wide_train / vt_decode_mlp_bwd_wide / vt_rows_wgrad
-            c = _SampleGridFn.apply(grid, p, self.padding)
+            c = self._sample_train(p, grid, planes)
             c = self.fuser.forward_train(c_img, c)
             return (_DecodeMlpWideFn if self._wide else _DecodeMlpFn).apply(self, p, c, *self._params(False))
-        c = ops.sample_grid(grid, p, self.padding)
+        c = self._sample(p, grid, planes)
         c = self.fuser(c_img, 1, c, 1)
         return self._mlp_fwd(c, p)
 
