@@ -1360,6 +1360,40 @@ size_t vt_emd_workspace_bytes(int n, int m);
 int vt_emd_auction(const float *a, int N, const float *b, int M, int B, float eps_final, int max_rounds,
                    int *assign, float *prices, double *cost_f64, int *status, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------- */
+/* Voxel-input encoder front end (voxel_encoder.hip).                                                                            */
+/* Replaces: conv_in (Conv3d 1 -> C, kernel 3 with zero padding 1, or kernel 1), ReLU and the scatter_mean of the voxel features  */
+/* onto the grid or the planes in LocalVoxelEncoder.forward (src/encoder/voxels.py:56-119).  Exact f32.                           */
+/*   x [B,D1,D2,D3] f32 (every dimension >= 2, need not be equal); weight [C,1,k,k,k], bias [C], k = ksize in {1, 3};             */
+/*   f[b,c,v] = max(0, bias[c] + sum W x), one fused multiply-add per tap in (t1,t2,t3) order.                                    */
+/* A voxel's cell depends on the volume's shape alone, per axis and monotonically, so the caller supplies per-axis tables         */
+/* (vtaco_amd/ops/voxel_encoder.py builds them with the reference's f32 expressions):                                              */
+/*   index  int32 [D1 + D2 + D3]: a1[i1] | a2[i2] | a3[i3], each in [0, R);                                                        */
+/*   ranges int32 [3][R][2]: per axis and output index r the voxel indices [lo, hi) with a[i] == r (lo == hi: none).               */
+/* vt_voxel_encode_grid: grid_cl [B,R,R,R,C] channels-last, cell (z,y,x) = (a3,a2,a1), flat a1 + R (a2 + R a3); the value is the   */
+/*   sum of f over the cell's box in (i1,i2,i3) order divided by the voxel count, cells without a voxel exactly 0.0f.  Every cell  */
+/*   is written by the one launch (no clear pass).                                                                                */
+/* vt_voxel_encode_planes: plane_mask = xz (1) | xy (2) | yz (4), at least one; planes [P B,C,R,R], the present planes in that     */
+/*   order one after the other.  xz projects (p0,p2), xy (p0,p1), yz (p1,p2) (p_k along x's dimension k + 1); pixel [v][u] with u */
+/*   the first projected axis.  A cell is the mean over its two ranges times the whole dropped axis.  One launch for all planes.   */
+/* vt_voxel_encode_bwd: grad_weight [C,1,k,k,k] and grad_bias [C] from x, the weights and the upstream gradient of the grid        */
+/*   (grad_grid_cl, with grid_index / grid_ranges / Rg) and / or of the stacked planes (grad_planes, plane_index / plane_ranges /  */
+/*   Rp / plane_mask); NULL = that output had no gradient.  The pre-activation is recomputed (the forward saves nothing), masked   */
+/*   pre > 0; a voxel takes g[cell] / n from every output it fed.  Two deterministic stages through `workspace`                    */
+/*   (vt_voxel_encode_bwd_workspace_bytes bytes), no float atomics; both outputs are written, not accumulated into.  x gets no     */
+/*   gradient.                                                                                                                      */
+/* All three are bit-identical from run to run, and a scene's forward result does not depend on B.  C % 32 == 0, C <= 128, D <=    */
+/* 4096, R <= 1024 (VT_ERR_UNSUPPORTED otherwise, before any launch).                                                              */
+int vt_voxel_encode_grid(const float *x, int B, int D1, int D2, int D3, const float *weight, const float *bias, int C, int ksize,
+                         const int *ranges, int R, float *grid_cl, void *stream);
+int vt_voxel_encode_planes(const float *x, int B, int D1, int D2, int D3, const float *weight, const float *bias, int C, int ksize,
+                           const int *ranges, int R, int plane_mask, float *planes, void *stream);
+size_t vt_voxel_encode_bwd_workspace_bytes(int B, int D1, int D2, int D3, int C);
+int vt_voxel_encode_bwd(const float *x, int B, int D1, int D2, int D3, const float *weight, const float *bias, int C, int ksize,
+                        const float *grad_grid_cl, const int *grid_index, const int *grid_ranges, int Rg,
+                        const float *grad_planes, const int *plane_index, const int *plane_ranges, int Rp, int plane_mask,
+                        float *grad_weight, float *grad_bias, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

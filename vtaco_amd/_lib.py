@@ -372,6 +372,10 @@ SIGNATURES = {
     "vt_chamfer_nn": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "vt_emd_workspace_bytes": (_SZ, [_I, _I]),
     "vt_emd_auction": (_I, [_VP, _I, _VP, _I, _I, _F, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_voxel_encode_grid": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _I, _I, _VP, _I, _VP, _VP]),
+    "vt_voxel_encode_planes": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP]),
+    "vt_voxel_encode_bwd_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "vt_voxel_encode_bwd": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _SZ, _VP]),
 }
 
 _lib = None

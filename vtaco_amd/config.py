@@ -34,7 +34,9 @@ def get_inputs_field(mode, cfg):
         return cls(d['pointcloud_file'], transform, multi_files=d['multi_files'])
     if kind == 'idx':
         return data.IndexField()
-    if kind in ('pointcloud_crop', 'voxels'):
+    if kind == 'voxels':
+        return data.VoxelsField(d['voxels_file'])
+    if kind == 'pointcloud_crop':
         raise NotImplementedError("get_inputs_field: input_type '%s' is not built (no shipped VTacO config uses it)" % kind)
     raise ValueError('Invalid input type (%s)' % kind)
 

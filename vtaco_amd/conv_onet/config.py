@@ -97,7 +97,8 @@ def get_inferencer(model, optimizer, generator, cfg, device, **kwargs):
 
 def get_data_fields(mode, cfg):
     """Method-specific fields of a sample (reference conv_onet/config.py:272-318): the query points
-    with occupancies ('points'), and for val / test the IoU points ('points_iou')."""
+    with occupancies ('points'), and for val / test / vis the IoU points ('points_iou') and, with ``data.voxels_file`` set, the
+    occupancy volume ('voxels': eval_step's iou_voxels)."""
     from .. import data
     d = cfg['data']
     if d['input_type'] == 'pointcloud_crop':
@@ -111,5 +112,5 @@ def get_data_fields(mode, cfg):
             fields['points_iou'] = data.PointsField(d['points_iou_file'], unpackbits=d['points_unpackbits'],
                                                     multi_files=d['multi_files'])
         if d.get('voxels_file') is not None:
-            raise VtError("get_data_fields: voxel (.binvox) fields are not built; set data.voxels_file: null")
+            fields['voxels'] = data.VoxelsField(d['voxels_file'])
     return fields

@@ -24,7 +24,7 @@ import torch
 from torch.nn import functional as F
 
 from .._lib import VtError
-from ..common import fingertips_in_object_frame
+from ..common import fingertips_in_object_frame, make_3d_grid
 from ..eval import compute_iou
 
 
@@ -426,6 +426,8 @@ class Trainer:
         """{'loss', 'iou'}: L1 loss on ``points`` and the reference's IoU (compute_iou: both sides cut at the mean ground-truth
         occupancy) on ``points_iou``; with ``with_img`` the query points carry tactile features assigned by the generator's rule
         (the reference's eval_step re-labels its points with libigl winding numbers instead, training.py:105-452: not mirrored).
+        A batch with ``'voxels'`` [B,D,D,D] adds 'iou_voxels' (training.py:374-390): the decoder at the voxel centres, cut at
+        ``threshold``, against the volume cut at 0.5.
         ``train_tactile``: {'loss', 'loss_depth'} of the t2d net (training.py:424-452)."""
         self.model.eval()
         dev = self.device
@@ -446,6 +448,14 @@ class Trainer:
                 occ_hat = torch.sigmoid(logits_at(data.get('points_iou')))
                 occ_iou = data.get('points_iou.occ')
                 out['iou'] = float(np.mean(compute_iou(occ_hat.cpu().numpy(), occ_iou.numpy(), self.threshold)))
+            voxels_occ = data.get('voxels')
+            if voxels_occ is not None:
+                # training.py:374-390: the decoder at the voxel centres of the unit cube's 32^3 convention, cut at the threshold,
+                # against the volume cut at 0.5 (compute_iou without a threshold: both sides are already boolean)
+                grid_pts = make_3d_grid((-0.5 + 1 / 64,) * 3, (0.5 - 1 / 64,) * 3, tuple(voxels_occ.shape[1:]))
+                grid_pts = grid_pts.unsqueeze(0).expand(voxels_occ.shape[0], -1, -1).contiguous()
+                occ_hat = torch.sigmoid(logits_at(grid_pts)) >= self.threshold
+                out['iou_voxels'] = float(np.mean(compute_iou((voxels_occ >= 0.5).cpu().numpy(), occ_hat.cpu().numpy())))
         return out
 
     def evaluate(self, val_loader):

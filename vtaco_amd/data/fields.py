@@ -10,6 +10,7 @@ import os
 
 import numpy as np
 
+from . import binvox
 from .core import Field
 
 
@@ -110,6 +111,24 @@ class PartialPointCloudField(Field):
         keep = (points[:, side] - lo) <= length
         out = {None: points[keep], 'normals': normals[keep]}
         return self.transform(out) if self.transform is not None else out
+
+    def check_complete(self, files):
+        return self.file_name in files
+
+
+class VoxelsField(Field):
+    """A ``.binvox`` occupancy volume as float32 [D,D,D] (fields.py:179-218)."""
+
+    def __init__(self, file_name, transform=None):
+        self.file_name, self.transform = file_name, transform
+
+    def load(self, model_path, idx, category):
+        with open(os.path.join(model_path, self.file_name), 'rb') as f:
+            voxels = binvox.read_as_3d_array(f)
+        voxels = voxels.data.astype(np.float32)
+        if self.transform is not None:
+            voxels = self.transform(voxels)
+        return voxels
 
     def check_complete(self, files):
         return self.file_name in files
