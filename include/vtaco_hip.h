@@ -1394,6 +1394,33 @@ int vt_voxel_encode_bwd(const float *x, int B, int D1, int D2, int D3, const flo
                         const float *grad_planes, const int *plane_index, const int *plane_ranges, int Rp, int plane_mask,
                         float *grad_weight, float *grad_bias, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the PointConv baseline: point-feature sampler (point_sample.hip) and PointNet++ geometry (pointnetpp.hip) ------------------ */
+/* The sampler: out [B,M,C], c_m = sum_n w[m,n] fea_n / sum_n w[m,n] over the cloud [B,N,3] with features fea [B,N,C]              */
+/*   (reference decoder.py:468-485).  gaussian != 0: w = exp(-(|p_n - q_m| + 10e-6)^2 / gaussian_val^2), evaluated with the query's  */
+/*   largest exponent subtracted (shift): equal to the reference wherever its own sum does not underflow, finite where it returns  */
+/*   NaN.  gaussian == 0: w = 1 / (|p_n - q_m| + 10e-6), shift = 0.  Queries: q [B,M,3], or NULL with the lattice (lattice_nx,       */
+/*   lattice_box, lattice_first, M) in vt_sample_grid's arithmetic -- bit for bit the point form on those points.  shift, sum [B,M]: */
+/*   what the backward rebuilds the normalised weights from.  Exact-f32 matrix products.  C % 32 == 0, C <= 256, N >= 1.           */
+/* The backward: grad_fea [B,N,C] = sum_m (w[m,n] / sum_m) grad_c [b,m,:]; ordered sums, no float atomics, every element written.   */
+/*   Neither q nor the cloud gets a gradient.  workspace: vt_point_sample_bwd_workspace_bytes(B, M, N, C) bytes (0 for M <= 512).   */
+int vt_point_sample_fwd(const float *q, int64_t M, int lattice_nx, float lattice_box, int64_t lattice_first,
+                        const float *cloud, const float *fea, int B, int64_t N, int C, int gaussian, double gaussian_val,
+                        float *out, float *shift, float *sum, void *stream);
+size_t vt_point_sample_bwd_workspace_bytes(int B, int64_t M, int64_t N, int C);
+int vt_point_sample_bwd(const float *q, int64_t M, const float *cloud, int B, int64_t N, int C, int gaussian, double gaussian_val,
+                        const float *shift, const float *sum, const float *grad_c, float *grad_fea,
+                        void *workspace, size_t workspace_bytes, void *stream);
+/* Farthest-point sampling (pointnetpp.py:188-209): out [B,npoint] i64, out[b,0] = start[b] (i64, clamped into the cloud), then    */
+/*   the arg-max of the running minimum of ((dx dx + dy dy) + dz dz), the lowest index among equal maxima.  dist_ws: [B,N] floats    */
+/*   of scratch.  N < npoint is VT_ERR_INVALID.                                                                                    */
+int vt_fps(const float *xyz, int B, int N, int npoint, const int64_t *start, float *dist_ws, int64_t *out, void *stream);
+/* Ball query (pointnetpp.py:212-232): out [B,S,nsample] i64, per centre the lowest nsample indices n with                         */
+/*   |xyz_n - centre|^2 <= (float)(radius^2) in ascending order, a short row padded with its first entry (an empty one with 0).    */
+int vt_ball_query(const float *xyz, int B, int N, const float *centres, int S, double radius, int nsample, int64_t *out, void *stream);
+/* The k = min(3, S) nearest sources src [B,S,3] of every target tgt [B,N,3] (pointnetpp.py:84-90): idx [B,N,k] i64 in ascending     */
+/*   distance (the lowest index among equals), weight [B,N,k] = (1 / (d^2 + 1e-8)) / their sum.                                    */
+int vt_three_nn(const float *tgt, int B, int N, const float *src, int S, int64_t *idx, float *weight, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -376,6 +376,12 @@ SIGNATURES = {
     "vt_voxel_encode_planes": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP]),
     "vt_voxel_encode_bwd_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "vt_voxel_encode_bwd": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_point_sample_fwd": (_I, [_VP, _I64, _I, _F, _I64, _VP, _VP, _I, _I64, _I, _I, _D, _VP, _VP, _VP, _VP]),
+    "vt_point_sample_bwd_workspace_bytes": (_SZ, [_I, _I64, _I64, _I]),
+    "vt_point_sample_bwd": (_I, [_VP, _I64, _VP, _I, _I64, _I, _I, _D, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_fps": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
+    "vt_ball_query": (_I, [_VP, _I, _I, _VP, _I, _D, _I, _VP, _VP]),
+    "vt_three_nn": (_I, [_VP, _I, _I, _VP, _I, _VP, _VP, _VP]),
 }
 
 _lib = None

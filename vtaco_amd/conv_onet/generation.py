@@ -272,6 +272,15 @@ class Generator3D(object):
     def eval_lattice(self, c, nx, c_img_all=None, first=0, count=None, out=None):
         """Logits of the (1+padding)-box lattice, device tensor [count] (whole: nx^3).  ``out``: a contiguous float32 tensor of
         ``count`` elements to write them into."""
+        if isinstance(c, (tuple, list)):
+            # the PointConv baseline's (cloud, per-point features): the lattice form of the point-feature sampler, slab by slab
+            self._refuse_point_tactile("eval_lattice", c_img_all)
+            if c[1].shape[0] != 1:
+                raise VtError("eval_lattice: one scene at a time (the lattice is per scene)")
+            if count == 0:
+                return torch.empty(0, dtype=torch.float32, device=c[1].device)
+            return self.model.decoder.decode_lattice(c, nx, box=1 + self.padding, first=first, count=count, out=out,
+                                                     precision=self.decode_precision).reshape(-1)
         if isinstance(c, dict) and set(c) != {'grid'}:
             # plane features (alone or next to the volume): the decoder's sampled route, slab by slab (LocalDecoder.decode_lattice)
             one = next(iter(c.values()))
@@ -298,6 +307,20 @@ class Generator3D(object):
         if self._plane_model():
             raise VtError(f"Generator3D.{what}: the encoder returns plane features {self.model.encoder.planes}, which this route does "
                           f"not take ({why}); generate_obj_mesh_wnf without with_img and eval_lattice decode them")
+
+    def _point_model(self):
+        """True for the PointConv baseline: the decoder takes (cloud, per-point features) instead of a grid or planes."""
+        from .models.decoder import LocalPointDecoder
+        return isinstance(getattr(self.model, "decoder", None), LocalPointDecoder)
+
+    def _refuse_point(self, what, why):
+        if self._point_model():
+            raise VtError(f"Generator3D.{what}: not built for the PointConv baseline (pointnet_plus_plus / simple_local_point): {why}")
+
+    def _refuse_point_tactile(self, what, c_img_all=None):
+        if self.with_img or c_img_all is not None:
+            raise VtError(f"Generator3D.{what}: the PointConv decoder has no tactile variant (the reference's LocalPointDecoder has "
+                          "neither forward_img nor a contact head)")
 
     def extract_mesh(self, value_grid, level=None):
         """``measure.marching_cubes(value_grid, gradient_direction='ascent')`` followed by
@@ -458,6 +481,8 @@ class Generator3D(object):
         (launch-bound otherwise); only the data-dependent output sizing leaves the graph.  Safe across weight
         updates and interleaved eager calls of other shapes (see ``_scene_graph``).  Dense extraction only."""
         self._refuse_mise("generate_mesh_graphed")
+        self._refuse_point("generate_mesh_graphed", "the encoder draws its farthest-point start indices from the CPU generator, once "
+                           "per scene; a captured graph would replay one draw for ever")
         self._refuse_planes("generate_mesh_graphed", "the captured scene graph holds the fused volume decode, vt_decode_fwd*")
         self._eval_mode()
         nx = self.resolution0 * 4
@@ -478,6 +503,8 @@ class Generator3D(object):
         Dense extraction only."""
         from .. import dist as vdist
         self._refuse_mise("generate_obj_mesh_sharded")
+        self._refuse_point("generate_obj_mesh_sharded", "every rank would draw its own farthest-point start indices, so the slabs of "
+                           "one value grid would belong to different encodings")
         self._refuse_planes("generate_obj_mesh_sharded", "its slabs are aligned for the fused volume decode, vt_decode_fwd*")
         self._eval_mode()
         nx = self.resolution0 * 4
@@ -514,6 +541,7 @@ class Generator3D(object):
         successful fingertip (``mode='nearest'``, radius 0.05: VTacOH, :186-200) from ``vt_tactile_assign``, and the
         decoder reads ``finger_feats [F,C]`` by id (``vt_decode_fwd_ids``): 1 byte per point instead of 4*C.
         ``anchors [F,K,3]`` (K = 1 for 'nearest'), ``count [F]`` valid anchors per finger, ``success [F]``."""
+        self._refuse_point("generate_obj_mesh_tactile", "the PointConv decoder has no tactile variant")
         self._eval_mode()
         nx = self.resolution0 * 4
         setup = {'feats': finger_feats, 'anchors': anchors, 'success': success, 'mode': mode,
@@ -735,11 +763,13 @@ class Generator3D(object):
             return self._generate_mise(data, c_img_all)
         nx = self.resolution0 * 4                       # generation.py:120
         inputs = data.get('inputs').to(self.device)
+        if self._point_model():
+            self._refuse_point_tactile("generate_obj_mesh_wnf", c_img_all)
         if self.with_img:
             self._refuse_planes("generate_obj_mesh_wnf(with_img)", "the tactile decodes (fc_p_img, finger ids) sample a volume")
         if self.with_img and c_img_all is None:
             return self._generate_tactile(data)
-        if (not self.with_img and not self._plane_model() and self._graphs_allowed() and inputs.dim() == 3 and inputs.shape[0] == 1
+        if (not self.with_img and not self._plane_model() and not self._point_model() and self._graphs_allowed() and inputs.dim() == 3 and inputs.shape[0] == 1
                 and self._worth_capturing((tuple(inputs.shape), nx, self.decode_precision))):
             # the visual branch: the same launches replayed as one hipGraph per (cloud shape, lattice) -- 1.1 instead of 1.5 ms
             return self.generate_mesh_graphed(inputs)
@@ -795,6 +825,7 @@ class Generator3D(object):
         """(c, setup) of a tactile scene: the shape encoder's output and the branch's finger features, anchors and rule, with the
         encoders overlapped on the side streams (see _generate_tactile)."""
         self._eval_mode()
+        self._refuse_point("generate_obj_mesh_wnf(with_img)", "the PointConv decoder has no tactile variant")
         self._refuse_planes("generate_obj_mesh_wnf(with_img)", "the tactile decodes read the finger features in vt_decode_fwd_ids / "
                             "the fuser's id kernels, which sample a volume")
         inputs = data.get('inputs').to(self.device)
@@ -836,6 +867,16 @@ class Generator3D(object):
         the decoder reads the finger's feature by id."""
         dec = self.model.decoder
         prec = self._mise_precision()
+        if isinstance(c, (tuple, list)):
+            # the PointConv baseline: the point form of the sampler (vt_point_sample_fwd), then the MLP on given features
+            if setup is not None:
+                raise VtError("Generator3D.mise_evaluator: the PointConv decoder has no tactile variant")
+            cloud, fea = dec._pair(c)
+
+            def evaluate_cloud(ids, pts):
+                p = pts.reshape(1, -1, 3)
+                return dec._mlp_given(dec._sample_points(cloud, fea, p), p, precision=prec).reshape(-1)
+            return evaluate_cloud
         if isinstance(c, dict) and set(c) != {'grid'}:
             # plane features: the point path of the decoder's sampled route (vt_sample_planes, then the MLP on given features)
             if setup is not None:

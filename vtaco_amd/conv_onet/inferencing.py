@@ -131,6 +131,10 @@ class Inferencer(object):
         if getattr(self.generator, "extraction", "dense") != "dense":
             raise VtError("Inferencer: the session keeps the dense nx^3 lattice; the generator has extraction='mise' "
                           "(use a generator with extraction='dense')")
+        from .models.decoder import LocalPointDecoder
+        if isinstance(getattr(self.model, "decoder", None), LocalPointDecoder):
+            raise VtError("Inferencer: the PointConv baseline (pointnet_plus_plus / simple_local_point) has no tactile variant, and the "
+                          "session's touches are tactile features merged into the lattice")
         enc = getattr(self.model, "encoder", None)
         if enc is not None and getattr(enc, "planes", ['grid']) != ['grid']:
             raise VtError(f"Inferencer: the encoder returns plane features {enc.planes}; the session's incremental decodes read the finger "

@@ -9,14 +9,15 @@ from torch import nn
 
 from . import decoder
 
-# same registry names as the reference (models/__init__.py:7-12); the crop / PointConv
-# baselines are out of scope
+# same registry names as the reference (models/__init__.py:7-12); the crop baseline
+# ('simple_local_crop') is out of scope
 # A/B knob: "0" keeps the reference's per-scene loop over the tactile feature encoder (one pass over all scenes' images otherwise)
 _SCENE_BATCH = os.environ.get("VTACO_TACTILE_SCENE_BATCH", "1") != "0"
 
 decoder_dict = {
     'simple_local': decoder.LocalDecoder,
     'attention_local': decoder.AttentionDecoder,
+    'simple_local_point': decoder.LocalPointDecoder,
 }
 
 

@@ -526,3 +526,113 @@ class AttentionDecoder(LocalDecoder):
             wp = self._wide_precision(prec)
             return ops.decode_mlp_fwd(c, self._blob(precision=wp), p, precision=wp, wide=(self.hidden_size, self.n_blocks, self.leaky))
         return ops.decode_mlp_fwd(c, self._blob(precision=prec), p, precision=prec)
+
+
+class _PointSampleFn(torch.autograd.Function):
+    """The point-feature sampler (vt_point_sample_fwd / vt_point_sample_bwd), differentiable in the features alone: neither the
+    queries nor the cloud -- the network's input -- gets a gradient."""
+
+    @staticmethod
+    def forward(ctx, cloud, fea, p, sample_mode, gaussian_val):
+        c, shift, total = ops.points.point_sample(cloud, fea, pts=p, sample_mode=sample_mode, gaussian_val=gaussian_val, want_saved=True)
+        ctx.saved = (cloud.detach(), p.detach(), shift, total)
+        ctx.mode = (sample_mode, gaussian_val)
+        return c
+
+    @staticmethod
+    def backward(ctx, grad_c):
+        cloud, p, shift, total = ctx.saved
+        return None, ops.points.point_sample_bwd(cloud, p, shift, total, grad_c, *ctx.mode), None, None, None
+
+
+class LocalPointDecoder(LocalDecoder):
+    """``simple_local_point``, the decoder of the PointConv baseline (reference decoder.py:427-515): the conditioning feature of a
+    query is the normalised kernel-weighted sum of per-point features over the whole input cloud -- ``c = (cloud [B,N,3], features
+    [B,N,c_dim])``, what ``PointNetPlusPlus`` returns -- followed by LocalDecoder's conditioned MLP on given features.
+
+    ``sample_mode='gaussian'`` (needs ``gaussian_val``): w = exp(-(|p_n - q| + 10e-6)^2 / gaussian_val^2); any other mode:
+    w = 1 / (|p_n - q| + 10e-6).  The Gaussian quotient is evaluated with the query's largest exponent subtracted: where the
+    reference's sum underflows and it returns NaN (nearest cloud point beyond ~10 gaussian_val) this returns the finite limit.
+    The sampler is vt_point_sample_fwd / _bwd (``VTACO_POINTCONV=host``: its torch restatement); the reference's split into 10 000
+    queries changes no value and is not mirrored.  ``padding`` and ``with_contact`` (what get_model passes) are swallowed."""
+
+    def __init__(self, dim=3, c_dim=128, hidden_size=256, leaky=False, n_blocks=5, sample_mode='gaussian', **kwargs):
+        if dim != 3:
+            raise VtError("LocalPointDecoder: only dim=3 is built")
+        if c_dim == 0:
+            raise VtError("LocalPointDecoder: c_dim = 0 (an unconditioned MLP) is not built")
+        if hidden_size % 32 or c_dim % 32 or not 32 <= hidden_size <= 256 or not 32 <= c_dim <= 256:
+            raise VtError(f"LocalPointDecoder: the MLP-on-features kernels take hidden_size and c_dim multiples of 32 up to 256 "
+                          f"(got {hidden_size} / {c_dim})")
+        if sample_mode == 'gaussian' and kwargs.get('gaussian_val') is None:
+            raise VtError("LocalPointDecoder: sample_mode 'gaussian' needs gaussian_val")
+        super().__init__(dim=dim, c_dim=c_dim, hidden_size=hidden_size, n_blocks=n_blocks, leaky=leaky, sample_mode='bilinear')
+        del self.fc_p_img                                   # the reference class has fc_p, fc_c, blocks and fc_out alone
+        self.sample_mode = sample_mode
+        self.gaussian_val = float(kwargs['gaussian_val']) if sample_mode == 'gaussian' else None
+
+    @staticmethod
+    def _pair(c):
+        if not isinstance(c, (tuple, list)) or len(c) != 2:
+            raise VtError("LocalPointDecoder: c must be the pair (cloud [B,N,3], features [B,N,c_dim]) the pointnet_plus_plus encoder returns")
+        cloud, fea = c
+        if not fea.is_cuda:
+            raise VtError(f"LocalPointDecoder: inputs must live on a HIP device (got {fea.device})")
+        return cloud, fea
+
+    def _sample_points(self, cloud, fea, p=None, lattice=None):
+        from ... import pointconv_host as host
+        fn = ops.points.point_sample if host.form("sample" if lattice is None else "sample_lattice") == "hip" else host.point_sample
+        return fn(cloud, fea, pts=p, lattice=lattice, sample_mode=self.sample_mode, gaussian_val=self.gaussian_val)
+
+    def forward(self, p, c, **kwargs):
+        """logits [B,M] for the queries p [B,M,3] (decoder.py:487-515)."""
+        from ... import pointconv_host as host
+        cloud, fea = self._pair(c)
+        p = p.float()
+        if torch.is_grad_enabled() and (fea.requires_grad or any(q.requires_grad for q in self.parameters())):
+            if host.form("sample") == "hip":
+                feat = _PointSampleFn.apply(cloud, fea.float(), p, self.sample_mode, self.gaussian_val)
+            else:
+                feat = self._sample_points(cloud.detach(), fea.float(), p)
+            return (_DecodeMlpWideFn if self._wide else _DecodeMlpFn).apply(self, p, feat.contiguous(), *self._params(False))
+        with torch.no_grad():
+            return self._mlp_given(self._sample_points(cloud, fea, p), p)
+
+    def forward_img(self, p, c, c_img, **kwargs):
+        raise VtError("LocalPointDecoder.forward_img: the reference's PointConv decoder has no tactile variant (decoder.py:427-515)")
+
+    def forward_contact(self, p, c, **kwargs):
+        raise VtError("LocalPointDecoder.forward_contact: the reference's PointConv decoder has no contact head (decoder.py:427-515)")
+
+    def decode_lattice(self, c, nx, box=1.1, first=0, count=None, c_img=None, out=None, precision=None):
+        """Logits of ``box * make_3d_grid(...)[first:first+count]`` without materialising the points: the lattice form of the sampler,
+        then ops.planes.decode_mlp_lattice, slab by slab so the feature buffer stays at LATTICE_SLAB_POINTS rows."""
+        if c_img is not None:
+            raise VtError("LocalPointDecoder.decode_lattice: the PointConv decoder takes no tactile feature")
+        cloud, fea = self._pair(c)
+        count = nx ** 3 - first if count is None else count
+        precision = precision or self.precision
+        if precision == "f16f8":
+            precision = "f16x3"
+        B = fea.shape[0]
+        if out is None:
+            out = torch.empty((B, count), dtype=torch.float32, device=fea.device)
+        elif out.numel() != B * count or not out.is_contiguous():
+            raise VtError(f"LocalPointDecoder.decode_lattice: out must be a contiguous [B,count]=({B},{count}) tensor ([count] for one "
+                          f"scene), got {tuple(out.shape)}")
+        out = out.view(B, count)
+        step = max(1, LATTICE_SLAB_POINTS // B)
+        with torch.no_grad():
+            for lo in range(0, count, step):
+                n = min(step, count - lo)
+                lat = (nx, box, first + lo, n)
+                feat = self._sample_points(cloud, fea, lattice=lat)
+                if B == 1 or n == count:
+                    self._mlp_given(feat, None, precision, lattice=lat, out=out[:, lo:lo + n])
+                else:
+                    out[:, lo:lo + n] = self._mlp_given(feat, None, precision, lattice=lat)
+        return out
+
+    def decode_lattice_ids(self, *args, **kwargs):
+        raise VtError("LocalPointDecoder.decode_lattice_ids: the PointConv decoder takes no tactile feature")
