@@ -1249,7 +1249,8 @@ int vt_tactile_unet_bwd(const float *dout, const float *out, int n_img, int grou
 /*   vt_resblock_fc  x = [x1[n] | x2[n]] (x2 may be NULL: no concat);                */
 /*                   h = b0 + W0 relu(x); out[n] = b1 + W1 relu(h) + Ws x           */
 /*                   (ws NULL: identity shortcut, needs C1 + C2 == O).               */
-/* At most 256 hidden / output channels; weights must fit 64 KiB of LDS.             */
+/* At most 256 hidden / output channels; weights must fit 64 KiB of LDS             */
+/* (vt_linear_rows alone: 160 KiB).                                                  */
 /* ------------------------------------------------------------------------- */
 int vt_linear_rows(const float *x, const float *w, const float *b, int64_t N, int Cin, int Cout, float *out, void *stream);
 int vt_resblock_fc(const float *x1, int C1, const float *x2, int C2, int64_t N,

@@ -653,7 +653,12 @@ int vt_linear_rows(const float *x, const float *w, const float *b, int64_t N, in
     if (Cout > PN_THREADS) return vt_fail(VT_ERR_UNSUPPORTED, "vt_linear_rows: more than 256 output channels");
     const int pts = PN_THREADS / Cout;
     const size_t lds = ((size_t)Cin * (Cout | 1) + (size_t)pts * Cin) * sizeof(float);
-    if (lds > 64 * 1024) return vt_fail(VT_ERR_UNSUPPORTED, "vt_linear_rows: weights do not fit 64 KiB of LDS");
+    // (past the default 64 KiB -- 64 -> 256 channels needs 64.5 -- the launch asks for the device's 160 KiB, as the MFMA backward does)
+    if (lds > 160 * 1024) return vt_fail(VT_ERR_UNSUPPORTED, "vt_linear_rows: weights do not fit 160 KiB of LDS");
+    if (lds > 64 * 1024) {
+        const hipError_t e = vt_max_dyn_lds(reinterpret_cast<const void *>(&linear_rows_kernel), 160 * 1024);
+        if (e != hipSuccess) return vt_check(e, "vt_linear_rows: hipFuncSetAttribute");
+    }
     hipLaunchKernelGGL(linear_rows_kernel, dim3(rows_grid((int)N, pts)), dim3(PN_THREADS), lds, (hipStream_t)stream,
                        x, w, b, out, (int)N, Cin, Cout);
     return vt_check(hipGetLastError(), "vt_linear_rows");

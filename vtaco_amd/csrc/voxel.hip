@@ -321,6 +321,10 @@ __device__ __forceinline__ bool point_lane(int C, uint32_t npts, uint32_t &bt, i
     return lp < ppb && bt < npts;
 }
 
+// Trips of a cooperative block's channel loop `c = c0 + 256 * it`: the same for every thread of the block, because the loop body
+// holds barriers (a per-thread `c < C` bound gives the threads different trip counts once C > 256 is not a multiple of 256).
+__device__ __forceinline__ int channel_trips(int C) { return (C + 255) / 256; }
+
 // Large-segment role of block `tile` (0-based among the extra blocks): (scene b, sorted range [lo,hi)) or false
 __device__ __forceinline__ bool large_segment(uint32_t tile, int T, const int *order, const int *seg_lo, const int *seg_hi,
                                               uint32_t &b, int &lo, int &hi) {
@@ -369,17 +373,21 @@ pool_max_fwd_kernel(const float *feat, const int *order, const int *seg_lo, cons
     const int cl = C < 256 ? C : 256, G = 256 / cl, grp = threadIdx.x / cl, c0 = threadIdx.x - grp * cl;
     const int *ord = order + (size_t)b * T;
     const float *fb = feat + (size_t)b * T * C;
-    for (int c = c0; c < C; c += 256) {
+    // (the trip count is the block's, not the thread's: with C > 256 and not a multiple of 256 the threads past the last channel
+    // still meet every barrier, with `on` false)
+    const int trips = channel_trips(C);
+    for (int it = 0, c = c0; it < trips; ++it, c += 256) {
+        const bool on = grp < G && c < C;
         float m = 0.0f;
         int bj = -1;
-        if (grp < G)
+        if (on)
             for (int j = lo + grp; j < hi; j += G) {
                 const float v = fb[(size_t)ord[j] * C + c];
                 if (bj < 0 || v > m) { m = v; bj = j; }
             }
         red_m[threadIdx.x] = m; red_j[threadIdx.x] = bj;
         __syncthreads();
-        if (grp == 0) {
+        if (on && grp == 0) {
             for (int g = 1; g < G; ++g) {
                 const float v = red_m[g * cl + c0];
                 const int j = red_j[g * cl + c0];
@@ -388,24 +396,26 @@ pool_max_fwd_kernel(const float *feat, const int *order, const int *seg_lo, cons
             red_m[c0] = m; red_j[c0] = bj;
         }
         __syncthreads();
-        m = red_m[c0];
-        const int best = ord[red_j[c0]];
-        if (grp < G)
+        if (on) {
+            m = red_m[c0];
+            const int best = ord[red_j[c0]];
             for (int j = lo + grp; j < hi; j += G) {
                 const size_t o = ((size_t)b * T + ord[j]) * C + c;
                 out[o] = m;
                 if (argmax) argmax[o] = best;
             }
+        }
         __syncthreads();
     }
 }
 
 // sum over the sorted range [lo,hi) of src[b, ord[j], c] by the whole block (threads = channel lanes x groups); every
-// thread of channel lane c0 returns the total.  red: 256 floats of LDS.
+// thread of channel lane c0 returns the total.  red: 256 floats of LDS.  Called by ALL threads of the block (two barriers inside);
+// `on` = this thread has a channel and a group (grp < G && c < C), the others add nothing.
 __device__ __forceinline__ float block_segment_sum(const float *src_b, const int *ord, int lo, int hi, int C, int c, int cl, int G,
-                                                   int grp, int c0, float *red) {
+                                                   int grp, int c0, float *red, bool on) {
     float s = 0.0f;
-    if (grp < G)
+    if (on)
         for (int j = lo + grp; j < hi; j += G) s += src_b[(size_t)ord[j] * C + c];
     red[threadIdx.x] = s;
     __syncthreads();
@@ -464,9 +474,11 @@ pool_max_bwd_kernel(const float *grad_out, const int *argmax, const int *order, 
     if (!large_segment(blockIdx.x - small_blocks, T, order, seg_lo, seg_hi, b, lo, hi)) return;
     const int cl = C < 256 ? C : 256, G = 256 / cl, grp = threadIdx.x / cl, c0 = threadIdx.x - grp * cl;
     const int *ord = order + (size_t)b * T;
-    for (int c = c0; c < C; c += 256) {
-        const float tot = block_segment_sum(grad_out + (size_t)b * T * C, ord, lo, hi, C, c, cl, G, grp, c0, red);
-        if (grp < G)
+    const int trips = channel_trips(C);
+    for (int it = 0, c = c0; it < trips; ++it, c += 256) {
+        const bool on = grp < G && c < C;
+        const float tot = block_segment_sum(grad_out + (size_t)b * T * C, ord, lo, hi, C, c, cl, G, grp, c0, red, on);
+        if (on)
             for (int j = lo + grp; j < hi; j += G) {
                 const int t = ord[j];
                 const size_t o = ((size_t)b * T + t) * C + c;
@@ -564,9 +576,11 @@ scatter_mean_fwd_kernel(const float *feat, const int *idx, const int *order, con
     const int cl = C < 256 ? C : 256, G = 256 / cl, grp = threadIdx.x / cl, c0 = threadIdx.x - grp * cl;
     const int *ord = order + (size_t)b * T;
     const int id = idx[(size_t)b * T + ord[lo]];
-    for (int c = c0; c < C; c += 256) {
-        const float tot = block_segment_sum(feat + (size_t)(feat_scenes ? b % feat_scenes : b) * T * C, ord, lo, hi, C, c, cl, G, grp, c0, red);
-        if (grp == 0) grid[cell(b, c, id)] = tot / (float)(hi - lo);
+    const int trips = channel_trips(C);
+    for (int it = 0, c = c0; it < trips; ++it, c += 256) {
+        const bool on = grp < G && c < C;
+        const float tot = block_segment_sum(feat + (size_t)(feat_scenes ? b % feat_scenes : b) * T * C, ord, lo, hi, C, c, cl, G, grp, c0, red, on);
+        if (on && grp == 0) grid[cell(b, c, id)] = tot / (float)(hi - lo);
     }
 }
 

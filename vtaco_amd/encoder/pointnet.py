@@ -25,6 +25,22 @@ from .unet import UNet
 from .unet3d import UNet3D
 
 
+LDS_LIMIT = 64 * 1024
+
+
+def resblock_fc_lds_bytes(C, H, O, shortcut):
+    """Dynamic LDS of vt_resblock_fc (pointnet.hip): w0t [C][H|1], w1t [H][O|1], wst [C][O|1], rows [pts][C], hid [pts][H]."""
+    pts = 256 // max(H, O)
+    return 4 * (C * (H | 1) + H * (O | 1) + (C * (O | 1) if shortcut else 0) + pts * (C + H))
+
+
+def resblock_fc_bwd_lds_bytes(C, H, O, shortcut):
+    """Dynamic LDS of vt_resblock_fc_bwd's FMA kernel: w0t [C][H|1], w0n [H][C|1], w1n [O][H|1], wsn [O][C|1] and per row
+    x [C], dout [O], dh [H], h [H]."""
+    pts = 256 // max(C, H, O)
+    return 4 * (C * (H | 1) + H * (C | 1) + O * (H | 1) + (O * (C | 1) if shortcut else 0) + pts * (C + O + 2 * H))
+
+
 class _PoolMax(torch.autograd.Function):
     """pool_local (pointnet.py:116-132): per-voxel channel max, gathered back."""
 
@@ -262,11 +278,17 @@ class LocalPoolPointnet(nn.Module):
         return linear(self.fc_c, net)
 
     def _fused_mlp_fits(self):
-        """vt_resblock_fc keeps a block's three weight matrices in 64 KiB of LDS (hidden_dim <= 48 or so: the shipped
-        configs use 32); wider PointNets keep the nn.Linear (hipBLASLt) path."""
+        """True where the three launches of a block at C = 2 h, H = O = h all take the width: vt_resblock_fc (its three transposed
+        weight matrices and a few rows in 64 KiB of LDS), the vt_resblock_fc_bwd kernel the width takes -- the MFMA form at h = 32, which
+        has its own larger allowance, else the FMA form with four weight copies in 64 KiB -- and the weight gradient, which takes any
+        width (vt_resblock_wgrad up to 16 tiles, vt_rows_wgrad per product beyond).  The FMA backward is the tightest: hidden_dim <= 47
+        (the shipped configs use 32); wider PointNets keep the nn.Linear (hipBLASLt) path."""
         h = self.hidden_dim
-        floats = 2 * h * h + h * h + 2 * h * h + (256 // h if h <= 256 else 0) * 3 * h
-        return h <= 256 and floats * 4 <= 64 * 1024 and 2 * h <= 256
+        if h < 1 or 2 * h > 256:
+            return False
+        mfma = h == 32 and os.environ.get("VTACO_RESBLOCK_MFMA", "1")[:1] != "0"
+        bwd = 0 if mfma else resblock_fc_bwd_lds_bytes(2 * h, h, h, True)
+        return resblock_fc_lds_bytes(2 * h, h, h, True) <= LDS_LIMIT and bwd <= LDS_LIMIT
 
     @staticmethod
     def _linear_fits(lin):
