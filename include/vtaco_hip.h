@@ -1422,6 +1422,33 @@ int vt_ball_query(const float *xyz, int B, int N, const float *centres, int S, d
 /*   distance (the lowest index among equals), weight [B,N,k] = (1 / (d^2 + 1e-8)) / their sum.                                    */
 int vt_three_nn(const float *tgt, int B, int N, const float *src, int S, int64_t *idx, float *weight, void *stream);
 
+/* ---- mesh -> occupancy volume (voxelize.hip) ------------------------------------------------------------------------------------ */
+/* Stands where VoxelGrid.from_mesh (src/utils/voxels.py:16-42) calls voxelize_ray / voxelize_fill (:201-216), whose voxelize_surface  */
+/*   and voxelize_interior the reference never defines (upstream: Cython extensions), and scipy's binary_fill_holes (:215).          */
+/* verts [V,3] f32, faces [F,3] i32, loc_host [3] f64 on the HOST, scale > 0.  Grid units: g = ((v - loc) / scale + 0.5) * res per    */
+/*   component in that order, float64; voxel (i,j,k) is the closed box [i,i+1] x [j,j+1] x [k,k+1], centre (i+.5, j+.5, k+.5).        */
+/* vt_voxelize_surface: occ u8 [res][res][res] ([x][y][z]), cleared by the caller; a voxel is set to 1 when its box overlaps a       */
+/*   triangle by the 13-axis separating-axis test (3 box axes, the normal, 9 edge x box-axis products; equality = overlap), over     */
+/*   the triangle's bounding box clipped to the grid.  One wave per triangle; plain byte stores of 1.                                */
+/* vt_voxelize_interior: bits u32 [res][res][ceil(res / 32)] (bit k % 32 of word k / 32), cleared by the caller; parity of the       */
+/*   crossings of the +z ray from every voxel centre, per triangle: every column centre of the projected bounding box is tested      */
+/*   against the three edge functions -- each evaluated on the edge's canonical direction (lower vertex index first), negated when   */
+/*   the triangle walks it the other way, an exact 0 decided as if the centre sat at (+eps, +eps^2) -- and an inside column flips    */
+/*   the voxels k < clamp(ceil(z - .5), 0, res), z = (e0 z0 + e1 z1 + e2 z2) / A, with integer XOR atomics (bit-reproducible).        */
+/*   Triangles of projected area A == 0 are skipped.                                                                                  */
+/* vt_voxel_fill: ONE round of binary_fill_holes with 6-connectivity: six launches (three axes, forward and backward), one thread    */
+/*   per grid line; outside u8 [res]^3 (cleared by the caller before the first round) gains every unoccupied voxel that an outside   */
+/*   voxel, or the grid's boundary, reaches along a line; *changed (i32, cleared by the caller) becomes 1 when a voxel was gained.   */
+/*   The host repeats the round until changed stays 0; the filled volume is outside == 0.                                            */
+/* 1 <= res <= VT_VOXELIZE_MAX_RES (VT_ERR_INVALID otherwise, before any launch); V == 0 or F == 0 launches nothing.  Triangles with */
+/*   a vertex index outside [0, V) are skipped (the host refuses such meshes).                                                       */
+#define VT_VOXELIZE_MAX_RES 512
+int vt_voxelize_surface(const float *verts, int V, const int32_t *faces, int F, const double *loc_host, double scale, int res,
+                        uint8_t *occ, void *stream);
+int vt_voxelize_interior(const float *verts, int V, const int32_t *faces, int F, const double *loc_host, double scale, int res,
+                         uint32_t *bits, void *stream);
+int vt_voxel_fill(const uint8_t *occ, int res, uint8_t *outside, int32_t *changed, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

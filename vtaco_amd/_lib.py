@@ -382,6 +382,9 @@ SIGNATURES = {
     "vt_fps": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "vt_ball_query": (_I, [_VP, _I, _I, _VP, _I, _D, _I, _VP, _VP]),
     "vt_three_nn": (_I, [_VP, _I, _I, _VP, _I, _VP, _VP, _VP]),
+    "vt_voxelize_surface": (_I, [_VP, _I, _VP, _I, ctypes.POINTER(_D), _D, _I, _VP, _VP]),      # voxelize_surface, src/utils/voxels.py:202, 214 (undefined there)
+    "vt_voxelize_interior": (_I, [_VP, _I, _VP, _I, ctypes.POINTER(_D), _D, _I, _VP, _VP]),     # voxelize_interior, src/utils/voxels.py:204 (undefined there)
+    "vt_voxel_fill": (_I, [_VP, _I, _VP, _VP, _VP]),                                            # binary_fill_holes, src/utils/voxels.py:215
 }
 
 _lib = None

@@ -1,8 +1,8 @@
-"""Reader of the binvox voxel format (https://www.patrickmin.com/binvox/binvox.html), written from the format's description.
+"""Reader and writer of the binvox voxel format (https://www.patrickmin.com/binvox/binvox.html), written from the format's description.
 
 A file is an ASCII header -- ``#binvox 1``, ``dim d0 d1 d2``, ``translate tx ty tz``, ``scale s``, ``data`` -- followed by run-length
 pairs of bytes (value, count) that cover d0 * d1 * d2 voxels.  The voxels are stored with the y index running fastest and the z index
-next, so the array reshaped to ``dim`` is indexed [x][z][y]; ``read_as_3d_array`` hands back [x][y][z]."""
+next, so the array reshaped to ``dim`` is indexed [x][z][y]; ``read_as_3d_array`` hands back [x][y][z] and ``write`` takes [x][y][z]."""
 from __future__ import annotations
 
 import numpy as np
@@ -56,3 +56,31 @@ def read_as_3d_array(fp, fix_coords=True):
     if fix_coords:
         data = np.transpose(data, (0, 2, 1))
     return Voxels(data, dims, translate, scale)
+
+
+def write(voxels, fp):
+    """Write a ``Voxels`` (``data`` bool [x][y][z]) to an open binary file in the run-length format above: the header lines with
+    ``str`` of the numbers, then (value, count) byte pairs over the voxels in [x][z][y] order, a run ending at 255 voxels."""
+    data = np.asarray(voxels.data).astype(bool)
+    if data.ndim != 3:
+        raise ValueError('binvox.write: data must be a 3-D array')
+    head = '#binvox 1\ndim %s\ntranslate %s\nscale %s\ndata\n' % (
+        ' '.join(str(int(d)) for d in voxels.dims), ' '.join(str(t) for t in voxels.translate), str(voxels.scale))
+    fp.write(head.encode('ascii'))
+    flat = np.transpose(data, (0, 2, 1)).reshape(-1).astype(np.uint8)
+    if flat.size == 0:
+        return
+    starts = np.concatenate([[0], np.flatnonzero(flat[1:] != flat[:-1]) + 1])
+    lengths = np.diff(np.concatenate([starts, [flat.size]]))
+    values = flat[starts]
+    # a run of n voxels: n // 255 pairs of 255, then the remainder; like the reference's writer, a run that is followed by another one
+    # always ends with its remainder pair, even when that is (value, 0) -- readers repeat it zero times
+    full, rest = lengths // 255, lengths % 255
+    tail = rest > 0
+    tail[:-1] = True
+    pairs = full + tail
+    out_v = np.repeat(values, pairs)
+    out_c = np.full(out_v.size, 255, dtype=np.uint8)
+    ends = np.cumsum(pairs) - 1
+    out_c[ends[tail]] = rest[tail]
+    fp.write(np.stack([out_v, out_c], axis=1).astype(np.uint8).tobytes())

@@ -6,11 +6,11 @@ tensors.  No function here computes anything with torch ops.
 
 This file only re-exports: callers write ``ops.name`` and look the name up at call time.  A switch that is assigned at run time
 (``decode_train.GRID_SCATTER_SORTED``, ``unet3d._WGRAD_UP``) is read by its own module: assign it there, not to the copy here.
-``resnet_train``, ``planes``, ``voxel_encoder`` and ``points`` are submodules only: callers write ``ops.resnet_train.fwd``,
-``ops.planes.sample_planes``, ``ops.voxel_encoder.encode_grid``, ``ops.points.point_sample``.
+``resnet_train``, ``planes``, ``voxel_encoder``, ``points`` and ``voxelize`` are submodules only: callers write ``ops.resnet_train.fwd``,
+``ops.planes.sample_planes``, ``ops.voxel_encoder.encode_grid``, ``ops.points.point_sample``, ``ops.voxelize.surface``.
 """
 from . import (_base, decode, decode_train, decode_wide, fusion, labels, mano, mc, metrics, mise, nets2d, planes, pointnet, points, resnet_train, touch,  # noqa: F401
-               unet3d, voxel, voxel_encoder)
+               unet3d, voxel, voxel_encoder, voxelize)
 from ._base import *            # noqa: F401,F403
 from ._base import _c, _lib, _ptr_array     # noqa: F401
 from .decode import *           # noqa: F401,F403

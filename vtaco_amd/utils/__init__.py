@@ -1,0 +1,1 @@
+"""Utilities beside the hot path that mirror the reference's src/utils (``voxels``: occupancy volumes from meshes and back)."""
