@@ -1449,6 +1449,33 @@ int vt_voxelize_interior(const float *verts, int V, const int32_t *faces, int F,
                          uint32_t *bits, void *stream);
 int vt_voxel_fill(const uint8_t *occ, int res, uint8_t *outside, int32_t *changed, void *stream);
 
+/* ---- closest point on a triangle mesh (closest_point.hip) ------------------------------------------------------------------------- */
+/* Replaces: trimesh.proximity.closest_point(mesh, points) of the reference's eval_step (src/conv_onet/training.py:413-416: the          */
+/*   penetration depth of the predicted hand into the object mesh).                                                                    */
+/* verts [V,3] f32, faces [F,3] i32, pts [N,3] f32 -> d2 [N] f64: the minimum over the faces of the squared Euclidean distance to the   */
+/*   closed triangle, face [N] i32: the face that attains it (the lowest index among equal minima), closest [N,3] f64 (or NULL): the    */
+/*   point on it.  All arithmetic is float64 on the exactly converted inputs, unfused, in the order DESIGN.md's section                 */
+/*   "closest_point.hip" lists (tests/closest_point_ref.py, by_regions, restates it in numpy: the outputs are equal bit for bit).       */
+/*   A face whose normal (b - a) x (c - a) is exactly zero in float64 (a repeated index, collinear corners) is the union of its three   */
+/*   edges; no face produces NaN.  Queries and faces are both tiled; per-(query, face slab) partial minima are combined in ascending    */
+/*   slab order by a finish pass: no atomics on a result, run-to-run equal bits.                                                        */
+/* Errors: V <= 0 or F <= 0 (a mesh without faces has no closest point) or a NULL array is VT_ERR_INVALID and a short workspace          */
+/*   VT_ERR_WORKSPACE, before any launch; N == 0 launches nothing.  Face indices are checked on the device by the prepare pass: a face  */
+/*   with an index outside [0, V) is never dereferenced and takes no part, and sets bit 0 of the status word -- the int32 at the start  */
+/*   of `workspace` -- which the caller reads after the call (ops.metrics raises); bit 1: a scene record with V <= 0, F <= 0 or         */
+/*   F > max_F (that scene's outputs are d2 = +inf, face = -1).                                                                         */
+/* workspace: vt_closest_point_mesh_workspace_bytes(F, N) bytes (0 for F <= 0): the status word, the face records (112 bytes each) and  */
+/*   the partial minima.  vt_closest_point_mesh_slab_faces: the faces per slab the launch of B scenes uses (a multiple of 256).          */
+/* _scenes: B meshes of different sizes in one launch sequence: scenes = device array of B records {const float *verts; const int32_t   */
+/*   *faces; int32 V; int32 F} (vt_winding_number_scenes' 24-byte records), max_F >= every F, pts [B][N][3], d2 / face [B][N], closest   */
+/*   [B][N][3]; workspace: B * vt_closest_point_mesh_workspace_bytes(max_F, N) bytes.  Each scene equals its single call bit for bit.   */
+size_t vt_closest_point_mesh_workspace_bytes(int F, int64_t N);
+int vt_closest_point_mesh_slab_faces(int F, int64_t N, int B);
+int vt_closest_point_mesh(const float *verts, int V, const int32_t *faces, int F, const float *pts, int64_t N, double *d2, int32_t *face,
+                          double *closest, void *workspace, size_t workspace_bytes, void *stream);
+int vt_closest_point_mesh_scenes(const void *scenes, int B, int max_F, const float *pts, int64_t N, double *d2, int32_t *face, double *closest,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

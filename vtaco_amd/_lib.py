@@ -385,6 +385,10 @@ SIGNATURES = {
     "vt_voxelize_surface": (_I, [_VP, _I, _VP, _I, ctypes.POINTER(_D), _D, _I, _VP, _VP]),      # voxelize_surface, src/utils/voxels.py:202, 214 (undefined there)
     "vt_voxelize_interior": (_I, [_VP, _I, _VP, _I, ctypes.POINTER(_D), _D, _I, _VP, _VP]),     # voxelize_interior, src/utils/voxels.py:204 (undefined there)
     "vt_voxel_fill": (_I, [_VP, _I, _VP, _VP, _VP]),                                            # binary_fill_holes, src/utils/voxels.py:215
+    "vt_closest_point_mesh_workspace_bytes": (_SZ, [_I, _I64]),
+    "vt_closest_point_mesh_slab_faces": (_I, [_I, _I64, _I]),
+    "vt_closest_point_mesh": (_I, [_VP, _I, _VP, _I, _VP, _I64, _VP, _VP, _VP, _VP, _SZ, _VP]),   # trimesh.proximity.closest_point, training.py:415
+    "vt_closest_point_mesh_scenes": (_I, [_VP, _I, _I, _VP, _I64, _VP, _VP, _VP, _VP, _SZ, _VP]),
 }
 
 _lib = None

@@ -43,22 +43,30 @@ def rot_from_pyr(roll, pitch, yaw):
 
 def fingertips_in_object_frame(mano_joints, wrist_pos, wrist_euler, pc_ply):
     """The five fingertip joints (MANO joints 4, 8, 12, 16, 20) of every scene in the object's normalised frame
-    (training.py:543-556, generation.py:178-184): out of the MANO frame (fixed offset and rotation), out of the wrist
-    rotation, plus the wrist position, normalised like the object cloud (norm_pc_1, common.py:606-612).  5 x 3 numbers
-    per scene, host-side numpy in the reference's operation order.  [B,21,3], [B,3], [B,3], [B,M,3] -> float64 [B,5,3]."""
+    (training.py:543-556, generation.py:178-184): ``hand_in_object_frame`` of those joints.  5 x 3 numbers per scene.
+    [B,21,3], [B,3], [B,3], [B,M,3] -> float64 [B,5,3]."""
     import numpy as np
-    joints = np.asarray(mano_joints, dtype=np.float32)[:, [4, 8, 12, 16, 20]]
+    return hand_in_object_frame(np.asarray(mano_joints, dtype=np.float32)[:, [4, 8, 12, 16, 20]], wrist_pos, wrist_euler, pc_ply)
+
+
+def hand_in_object_frame(points, wrist_pos, wrist_euler, pc_ply):
+    """Hand points (MANO vertices, joints) in the object's normalised frame: out of the MANO frame (fixed offset and rotation), out of
+    the wrist rotation, plus the wrist position, normalised like the object cloud (norm_pc_1, common.py:606-612) -- what the reference
+    does to the fingertips (training.py:543-556) and, in eval_step, to the predicted hand before it tests it against the object mesh
+    (training.py:399-404).  Host-side numpy in the reference's operation order.  [B,K,3], [B,3], [B,3], [B,M,3] -> float64 [B,K,3]."""
+    import numpy as np
+    pts = np.asarray(points, dtype=np.float32)
     fixed = np.linalg.inv(rot_from_pyr(-np.pi / 2, np.pi / 2, 0.0))
-    tips = np.empty(joints.shape, dtype=np.float64)
-    for b in range(joints.shape[0]):
-        t = joints[b] - np.array([0.11, 0.005, 0], dtype=np.float32)
+    out = np.empty(pts.shape, dtype=np.float64)
+    for b in range(pts.shape[0]):
+        t = pts[b] - np.array([0.11, 0.005, 0], dtype=np.float32)
         t = np.linalg.inv(rot_from_pyr(*np.asarray(wrist_euler[b]))) @ (fixed @ t.T)
         t = t.T + np.asarray(wrist_pos[b])
         cloud = np.asarray(pc_ply[b])
         centroid = np.mean(cloud, axis=0)
         m = np.max(np.sqrt(np.sum((cloud - centroid) ** 2, axis=1)))
-        tips[b] = (t - centroid) / (2 * m)
-    return tips
+        out[b] = (t - centroid) / (2 * m)
+    return out
 
 
 def sensor_pose_inverse(cam_pos_t, cam_rot_t):

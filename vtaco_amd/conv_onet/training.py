@@ -422,12 +422,50 @@ class Trainer:
         feat = torch.gather(c_img, 1, ids.clamp(max=4).unsqueeze(-1).expand(-1, -1, c_img.shape[2]))
         return feat * (ids != 255).unsqueeze(-1).to(feat.dtype)
 
-    def eval_step(self, data, vf_dict=None):
+    def _hand_metrics(self, data, vf_dict):
+        """{'chamfer_distance', 'hand_joints_error', 'penetration_depth'} of a batch, each the mean over its scenes -- the hand terms of
+        the reference's eval_step (training.py:163-166, 393-419): the naive Chamfer of ``points.pc_hand`` against the predicted MANO
+        vertices (vt_chamfer_nn), the joint error against the MANO layer on the ground-truth pose, and the penetration depth of the
+        predicted hand, moved to the object's frame, into the scene's ground-truth mesh (vt_winding_number_scenes,
+        vt_closest_point_mesh_scenes), scaled by max ||pc_ply||."""
+        from ..common import hand_in_object_frame
+        from ..eval import chamfer_distance_device, hand_joint_error, penetration_depth_scenes
+        dev = self.device
+        if getattr(self.model, 'encoder_hand', None) is None:
+            raise VtError("Trainer.eval_step: hand_metrics needs a model with a hand encoder (encoder_hand)")
+        if vf_dict is None:
+            raise VtError("Trainer.eval_step: hand_metrics needs vf_dict, the ground-truth meshes by name")
+        for key in ('points.mano', 'points.pc_hand', 'points.wrist', 'inputs.pc_ply', 'points.name'):
+            if data.get(key) is None:
+                raise VtError(f"Trainer.eval_step: hand_metrics needs '{key}' in the batch")
+        mano_gt = data.get('points.mano').to(dev).float()
+        pc_hand = data.get('points.pc_hand').to(dev).float()
+        pc_ply = data.get('inputs.pc_ply').float().cpu().numpy()
+        names = data.get('points.name')
+        B = mano_gt.shape[0]
+        for name in names:
+            if name not in vf_dict:
+                raise VtError(f"Trainer.eval_step: hand_metrics needs the mesh '{name}' in vf_dict")
+        joints_gt = self.model.encode_hand_mano(torch.cat((mano_gt.new_zeros(B, 3), mano_gt[:, 6:]), dim=1))['mano_joints']
+        c_hand = self.model.encode_hand_inputs(data.get('inputs').to(dev))
+        pc_pred, joints_pred = c_hand['mano_verts'].float(), c_hand['mano_joints']
+        chamfer = chamfer_distance_device(pc_hand.contiguous(), pc_pred.contiguous())
+        verts = hand_in_object_frame(pc_pred.cpu().numpy(), mano_gt.cpu().numpy()[:, :3], data.get('points.wrist').cpu().numpy(), pc_ply)
+        scales = [np.max(np.sqrt(np.sum(pc_ply[b] ** 2, axis=1))) for b in range(B)]
+        depth = penetration_depth_scenes(torch.from_numpy(verts.astype(np.float32)).to(dev),
+                                         [self._device_mesh(vf_dict, names[b]) for b in range(B)], scales)
+        return {'chamfer_distance': float(chamfer.double().mean()),
+                'hand_joints_error': float(np.mean(hand_joint_error(joints_gt, joints_pred))),
+                'penetration_depth': float(np.mean(depth))}
+
+    def eval_step(self, data, vf_dict=None, hand_metrics=False):
         """{'loss', 'iou'}: L1 loss on ``points`` and the reference's IoU (compute_iou: both sides cut at the mean ground-truth
         occupancy) on ``points_iou``; with ``with_img`` the query points carry tactile features assigned by the generator's rule
         (the reference's eval_step re-labels its points with libigl winding numbers instead, training.py:105-452: not mirrored).
         A batch with ``'voxels'`` [B,D,D,D] adds 'iou_voxels' (training.py:374-390): the decoder at the voxel centres, cut at
         ``threshold``, against the volume cut at 0.5.
+        ``hand_metrics``: adds 'chamfer_distance', 'hand_joints_error' and 'penetration_depth' (training.py:393-419, ``_hand_metrics``);
+        needs a hand encoder, ``vf_dict`` and the batch's points.mano / pc_hand / wrist / name and inputs.pc_ply (VtError otherwise).
         ``train_tactile``: {'loss', 'loss_depth'} of the t2d net (training.py:424-452)."""
         self.model.eval()
         dev = self.device
@@ -435,6 +473,7 @@ class Trainer:
             if self.train_tactile:
                 loss, loss_depth, _ = self.compute_loss_tactile(data)
                 return {'loss': loss.item(), 'loss_depth': loss_depth.item()}
+            hand = self._hand_metrics(data, vf_dict) if hand_metrics else {}
             inputs = data.get('inputs').to(dev)
             c = self.model.encode_inputs(inputs)
 
@@ -456,13 +495,14 @@ class Trainer:
                 grid_pts = grid_pts.unsqueeze(0).expand(voxels_occ.shape[0], -1, -1).contiguous()
                 occ_hat = torch.sigmoid(logits_at(grid_pts)) >= self.threshold
                 out['iou_voxels'] = float(np.mean(compute_iou((voxels_occ >= 0.5).cpu().numpy(), occ_hat.cpu().numpy())))
+            out.update(hand)
         return out
 
-    def evaluate(self, val_loader):
-        """Mean of eval_step over a loader."""
+    def evaluate(self, val_loader, vf_dict=None, hand_metrics=False):
+        """Mean of eval_step over a loader (``hand_metrics`` with ``vf_dict``: its three hand terms as well)."""
         sums, n = {}, 0
         for batch in val_loader:
-            for k, v in self.eval_step(batch).items():
+            for k, v in self.eval_step(batch, vf_dict, hand_metrics=hand_metrics).items():
                 sums[k] = sums.get(k, 0.0) + v
             n += 1
         return {k: v / max(n, 1) for k, v in sums.items()}

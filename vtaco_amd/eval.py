@@ -1,5 +1,7 @@
-"""Evaluation metrics of the reference (src/common.py:11-91): the host functions as the reference writes them, and the
-device forms of the two the visualise block calls (chamfer_distance_device, earth_mover_distance_device: HIP kernels)."""
+"""Evaluation metrics of the reference (src/common.py:11-91, 142-154): the host functions as the reference writes them, the device
+forms of the two the visualise block calls (chamfer_distance_device, earth_mover_distance_device: HIP kernels), and the hand-object
+geometry of its eval_step (training.py:393-419) on vt_closest_point_mesh and vt_winding_number: signed_distance, penetration_depth,
+mesh_distances."""
 from __future__ import annotations
 
 import numpy as np
@@ -84,3 +86,89 @@ def earth_mover_distance_device(points1, points2, return_assignment=False):
     res = ops.emd_assignment(a, b)
     emd = float(res.emd[0]) if single else res.emd
     return (emd, res) if return_assignment else emd
+
+
+def hand_joint_error(joints_gt, joints_pred):
+    """Mean over the joints of the L2 distance between ground-truth and predicted joints (common.py:142-154), per scene:
+    [B,J,3] (or [J,3]) tensors or arrays -> float64 [B] (a float for one scene, as the reference returns it)."""
+    def host(j):
+        return (j.detach().cpu().numpy() if torch.is_tensor(j) else np.asarray(j)).astype(np.float64)
+    gt, pred = host(joints_gt), host(joints_pred)
+    if gt.shape != pred.shape or gt.ndim not in (2, 3) or gt.shape[-1] != 3:
+        from ._lib import VtError
+        raise VtError(f"hand_joint_error: expected two [B,J,3] joint sets (got {gt.shape}, {pred.shape})")
+    err = np.mean(np.linalg.norm(gt - pred, axis=-1), axis=-1)
+    return float(err) if gt.ndim == 2 else err
+
+
+def _inside_depth(d2, winding):
+    """Per row: the largest surface distance among the points whose winding number exceeds 0.5, 0 where none is inside."""
+    dist = torch.sqrt(d2) * (winding > 0.5).to(d2.dtype)
+    return dist.max(dim=-1)[0]
+
+
+def signed_distance(pts, verts, faces):
+    """Distance from every query point pts [N,3] to the mesh (verts [V,3] f32, faces [F,3] int; device tensors), float64 [N]: the square
+    root of vt_closest_point_mesh's minimum, negative where the winding number (vt_winding_number) exceeds 0.5 -- inside a closed,
+    outward-oriented mesh."""
+    from . import ops
+    pts = pts.float()
+    d2 = ops.metrics.closest_point_mesh(verts.float(), faces, pts, want_point=False).d2
+    inside = ops.winding_number(verts, faces, pts) > 0.5
+    dist = torch.sqrt(d2)
+    return torch.where(inside, -dist, dist)
+
+
+def penetration_depth(hand_verts, verts, faces, scale):
+    """Penetration depth of a hand into an object mesh as the reference's eval_step measures it (training.py:406-419): 0 when no hand
+    vertex has a winding number above 0.5; otherwise the largest distance to the surface (trimesh.proximity.closest_point there,
+    vt_closest_point_mesh here) among the vertices that have, times ``scale`` -- the reference passes max ||pc_ply|| of the uncentred
+    object cloud.  hand_verts [K,3] in the mesh's frame, verts [V,3] f32, faces [F,3] int on the device -> float."""
+    from . import ops
+    pts = hand_verts.float()
+    d2 = ops.metrics.closest_point_mesh(verts.float(), faces, pts, want_point=False).d2
+    return float(_inside_depth(d2, ops.winding_number(verts, faces, pts))) * float(scale)
+
+
+def penetration_depth_scenes(hand_verts, meshes, scales):
+    """``penetration_depth`` for a batch in one launch sequence each (vt_closest_point_mesh_scenes, vt_winding_number_scenes):
+    hand_verts [B,K,3] on the device, meshes = [(verts f32 [V,3], faces i32 [F,3])] per scene, scales [B] -> float64 array [B]."""
+    from . import ops
+    pts = hand_verts.float().contiguous()
+    d2 = ops.metrics.closest_point_mesh_scenes(meshes, pts, want_point=False).d2
+    depth = _inside_depth(d2, ops.winding_number_scenes(meshes, pts))
+    return depth.cpu().numpy() * np.asarray(scales, dtype=np.float64)
+
+
+def sample_mesh_surface(verts, faces, n, generator=None):
+    """n area-weighted samples of a mesh's surface with torch ops on the mesh's device: the face by searchsorted on the cumulative
+    areas, the point by square-root barycentrics (1 - sqrt(r1), sqrt(r1) (1 - r2), sqrt(r1) r2).  float64 arithmetic; returns
+    (points [n,3] f32, face [n] int64).  ``generator``: a torch.Generator on that device (the default generator otherwise)."""
+    v = verts.double()
+    f = faces.long()
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    area = 0.5 * torch.linalg.cross(b - a, c - a).norm(dim=1)
+    cum = torch.cumsum(area, dim=0)
+    r = torch.rand((n, 3), dtype=torch.float64, device=v.device, generator=generator)
+    face = torch.searchsorted(cum, r[:, 0] * cum[-1], right=True).clamp(max=f.shape[0] - 1)
+    s = torch.sqrt(r[:, 1])
+    w0, w1, w2 = (1 - s).unsqueeze(1), (s * (1 - r[:, 2])).unsqueeze(1), (s * r[:, 2]).unsqueeze(1)
+    return (a[face] * w0 + b[face] * w1 + c[face] * w2).float(), face
+
+
+def mesh_distances(pred_mesh, gt_mesh, n, generator=None, threshold=0.01):
+    """Surface-to-surface distances of two meshes, each (verts [V,3] f32, faces [F,3] int) on the device: ``n`` area-weighted samples
+    per mesh (``sample_mesh_surface``), every sample's distance to the OTHER mesh's surface (vt_closest_point_mesh) -- not to its
+    vertices, so a dense mesh is not favoured.  Returns floats: 'accuracy' (mean distance of the predicted samples to the ground-truth
+    mesh), 'completeness' (the other way), 'chamfer_l1' (their mean), 'f_score' (harmonic mean of the shares of samples within
+    ``threshold``, precision and recall; 0 when both are 0)."""
+    from . import ops
+    (pv, pf), (gv, gf) = pred_mesh, gt_mesh
+    sp, _ = sample_mesh_surface(pv, pf, n, generator)
+    sg, _ = sample_mesh_surface(gv, gf, n, generator)
+    acc = torch.sqrt(ops.metrics.closest_point_mesh(gv.float(), gf, sp, want_point=False).d2)
+    comp = torch.sqrt(ops.metrics.closest_point_mesh(pv.float(), pf, sg, want_point=False).d2)
+    precision, recall = float((acc <= threshold).double().mean()), float((comp <= threshold).double().mean())
+    accuracy, completeness = float(acc.mean()), float(comp.mean())
+    f_score = 2 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
+    return {'accuracy': accuracy, 'completeness': completeness, 'chamfer_l1': 0.5 * (accuracy + completeness), 'f_score': f_score}

@@ -8,6 +8,7 @@ This file only re-exports: callers write ``ops.name`` and look the name up at ca
 (``decode_train.GRID_SCATTER_SORTED``, ``unet3d._WGRAD_UP``) is read by its own module: assign it there, not to the copy here.
 ``resnet_train``, ``planes``, ``voxel_encoder``, ``points`` and ``voxelize`` are submodules only: callers write ``ops.resnet_train.fwd``,
 ``ops.planes.sample_planes``, ``ops.voxel_encoder.encode_grid``, ``ops.points.point_sample``, ``ops.voxelize.surface``.
+``ops.metrics`` is re-exported by the names of its ``__all__``; its closest-point launchers are reached as ``ops.metrics.closest_point_mesh``.
 """
 from . import (_base, decode, decode_train, decode_wide, fusion, labels, mano, mc, metrics, mise, nets2d, planes, pointnet, points, resnet_train, touch,  # noqa: F401
                unet3d, voxel, voxel_encoder, voxelize)
