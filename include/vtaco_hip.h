@@ -1476,6 +1476,41 @@ int vt_closest_point_mesh(const float *verts, int V, const int32_t *faces, int F
 int vt_closest_point_mesh_scenes(const void *scenes, int B, int max_F, const float *pts, int64_t N, double *d2, int32_t *face, double *closest,
                                  void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- rigid registration of point sets (icp.hip) ----------------------------------------------------------------------------------- */
+/* Replaces: src/utils/icp.py of the reference for 3-D points, B problems per call.  Everything is float64; every product, sum,         */
+/*   division and square root is a separate IEEE rounding in the fixed order DESIGN.md's section "icp.hip" lists (tests/icp_ref.py,    */
+/*   kernel_order, restates it in numpy: the outputs are equal bit for bit).  No atomics; run-to-run equal bits.  A 4x4 transform is    */
+/*   row-major; T p = ((T00 x + T01 y) + T02 z) + T03 per row.  1 <= N, M; 1 <= B <= 65535 (VT_ERR_INVALID otherwise, before any launch); */
+/*   a short workspace is VT_ERR_WORKSPACE.                                                                                            */
+/* vt_nn_points -- nearest_neighbor (icp.py:50-66; sklearn's kd-tree there): src [B][N][3], dst [B][M][3], T [B][4][4] or NULL (applied  */
+/*   to src first) -> d2 [B][N]: the squared distance (dx dx + dy dy) + dz dz to the nearest dst point, idx [B][N] i32: its index, the  */
+/*   lowest among equal minima.  Queries and targets are both tiled (256 queries per workgroup, targets staged through LDS in chunks of */
+/*   256 and read by broadcast); per-(query, slab) partial minima, then a finish pass in ascending slab order.  workspace:              */
+/*   vt_nn_points_workspace_bytes(N, M, B); vt_nn_points_slab_points: the targets per slab that launch uses (a multiple of 256).        */
+/* vt_icp_fit -- best_fit_transform (icp.py:5-47): a [B][N][3], b [B][M][3], idx [B][N] i32 or NULL: a_i corresponds to b[idx[i]] (an   */
+/*   index outside [0, M) is clamped into it), or to b_i (then M == N) -> T [B][4][4], the least-squares rigid map of a onto b.         */
+/*   Centroids and H = sum (a_i - abar)(b_i - bbar)^T by a two-stage reduction (chunks of 256 points summed by a fixed tree, the chunk  */
+/*   sums added in chunk order); the SVD of H by one-sided Jacobi rotations with a fixed sweep count, singular values descending;       */
+/*   R = V U^T, with V's last column negated when det R < 0 (icp.py:35-37); t = bbar - R abar.  H == 0 gives R = I.                     */
+/*   workspace: vt_icp_fit_workspace_bytes(N, B).                                                                                      */
+/* vt_icp -- icp (icp.py:69-121), the loop of :102-121 enqueued in full, no host synchronisation: A [B][N][3], Bp [B][M][3], init_pose    */
+/*   [B][4][4] or NULL (applied to the working copy of A first, :97-98).  Per iteration: neighbours of the working copy, the fit onto   */
+/*   them, working copy <- T working copy, then |prev_error - mean distance| < tolerance ends the problem (:113-116).  Every kernel of a */
+/*   later iteration returns at once for an ended problem: its working copy, distances, idx and counter stay while its batch mates go    */
+/*   on.  -> T [B][4][4] = vt_icp_fit(A, working copy) (:119), distances [B][N] (Euclidean) and idx [B][N] of the last executed         */
+/*   iteration, iterations [B] i32: its 0-based index (the reference's i; max_iterations - 1 when the cap is reached).                  */
+/*   max_iterations >= 1, tolerance >= 0.  workspace: vt_icp_workspace_bytes(N, M, B).                                                 */
+size_t vt_nn_points_workspace_bytes(int64_t N, int64_t M, int B);
+int vt_nn_points_slab_points(int64_t N, int64_t M, int B);
+int vt_nn_points(const double *src, int64_t N, const double *dst, int64_t M, int B, const double *T, double *d2, int32_t *idx, void *workspace,
+                 size_t workspace_bytes, void *stream);
+size_t vt_icp_fit_workspace_bytes(int64_t N, int B);
+int vt_icp_fit(const double *a, const double *b, int64_t N, int64_t M, const int32_t *idx, int B, double *T, void *workspace, size_t workspace_bytes,
+               void *stream);
+size_t vt_icp_workspace_bytes(int64_t N, int64_t M, int B);
+int vt_icp(const double *A, int64_t N, const double *Bp, int64_t M, int B, const double *init_pose, int max_iterations, double tolerance, double *T,
+           double *distances, int32_t *idx, int32_t *iterations, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

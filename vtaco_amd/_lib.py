@@ -389,6 +389,13 @@ SIGNATURES = {
     "vt_closest_point_mesh_slab_faces": (_I, [_I, _I64, _I]),
     "vt_closest_point_mesh": (_I, [_VP, _I, _VP, _I, _VP, _I64, _VP, _VP, _VP, _VP, _SZ, _VP]),   # trimesh.proximity.closest_point, training.py:415
     "vt_closest_point_mesh_scenes": (_I, [_VP, _I, _I, _VP, _I64, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_nn_points_workspace_bytes": (_SZ, [_I64, _I64, _I]),
+    "vt_nn_points_slab_points": (_I, [_I64, _I64, _I]),
+    "vt_nn_points": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _VP, _VP, _VP, _SZ, _VP]),                 # nearest_neighbor, utils/icp.py:50-66
+    "vt_icp_fit_workspace_bytes": (_SZ, [_I64, _I]),
+    "vt_icp_fit": (_I, [_VP, _VP, _I64, _I64, _VP, _I, _VP, _VP, _SZ, _VP]),                         # best_fit_transform, utils/icp.py:5-47
+    "vt_icp_workspace_bytes": (_SZ, [_I64, _I64, _I]),
+    "vt_icp": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _I, _D, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),       # icp, utils/icp.py:69-121
 }
 
 _lib = None

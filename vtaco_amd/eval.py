@@ -172,3 +172,28 @@ def mesh_distances(pred_mesh, gt_mesh, n, generator=None, threshold=0.01):
     accuracy, completeness = float(acc.mean()), float(comp.mean())
     f_score = 2 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
     return {'accuracy': accuracy, 'completeness': completeness, 'chamfer_l1': 0.5 * (accuracy + completeness), 'f_score': f_score}
+
+
+def mesh_distances_aligned(pred_mesh, gt_mesh, n, generator=None, threshold=0.01, max_iterations=20, tolerance=1e-3):
+    """``mesh_distances`` after a rigid registration of the predicted mesh onto the ground truth, so that a pose offset of the prediction
+    does not read as shape error.  Both surfaces are sampled exactly as ``mesh_distances`` samples them; ``ops.icp.icp`` maps the
+    predicted samples onto the ground-truth samples (vt_icp, float64); its T moves the predicted vertices, per component
+    ((T00 x + T01 y) + T02 z) + T03 in float64, rounded to float32.  Returns ``mesh_distances`` of the moved mesh against the ground truth
+    from the same random draws (the generator is put back to where the sampling began, so it ends where one ``mesh_distances`` call
+    leaves it), plus 'transform' (4x4 float64 numpy array) and 'icp_iterations' (int, the 0-based index of the last executed iteration)."""
+    from . import ops
+    (pv, pf), (gv, gf) = pred_mesh, gt_mesh
+    state = generator.get_state() if generator is not None else torch.cuda.get_rng_state(pv.device)
+    sp, _ = sample_mesh_surface(pv, pf, n, generator)
+    sg, _ = sample_mesh_surface(gv, gf, n, generator)
+    fit = ops.icp.icp(sp, sg, max_iterations=max_iterations, tolerance=tolerance)
+    T, v = fit.T, pv.double()
+    moved = torch.stack([((T[r, 0] * v[:, 0] + T[r, 1] * v[:, 1]) + T[r, 2] * v[:, 2]) + T[r, 3] for r in range(3)], dim=1).float()
+    if generator is not None:
+        generator.set_state(state)
+    else:
+        torch.cuda.set_rng_state(state, pv.device)
+    out = mesh_distances((moved, pf), gt_mesh, n, generator, threshold)
+    out['transform'] = T.cpu().numpy()
+    out['icp_iterations'] = int(fit.iterations)
+    return out
