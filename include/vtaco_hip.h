@@ -1511,6 +1511,43 @@ size_t vt_icp_workspace_bytes(int64_t N, int64_t M, int B);
 int vt_icp(const double *A, int64_t N, const double *Bp, int64_t M, int B, const double *init_pose, int max_iterations, double tolerance, double *T,
            double *distances, int32_t *idx, int32_t *iterations, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- mesh topology (mesh_topo.hip) ------------------------------------------------------------------------------------------------ */
+/* Replaces: what the reference gets from wrapping its meshes in trimesh.Trimesh -- split, area, volume, is_watertight, euler_number.   */
+/* faces [F,3] i32, vertices [V,3] f32 (verts_f64 = 0) or f64 (1) as vt_mc_emit leaves them.  1 <= V, F (VT_ERR_INVALID otherwise,     */
+/*   before any launch); a short workspace is VT_ERR_WORKSPACE.  A face with an index outside [0, V) is never dereferenced: the calls   */
+/*   that read a count back return VT_ERR_INVALID for such a mesh, the two asynchronous ones leave the face out.                      */
+/* vt_mesh_components: labels [V] i32, the smallest vertex index of the vertex's connected component (vertices joined by a face edge;  */
+/*   an unreferenced vertex keeps its own index).  Hooking by integer atomicMin on roots and pointer jumping, one launch per round,   */
+/*   repeated until a hooking round changed nothing (the flags are read in batches; there is no cap); *rounds: the rounds run.        */
+/*   Waits for the stream.                                                                                                            */
+/* vt_mesh_component_table: *n_components = the roots that own a face; comp_of_vertex [V]: the rank of the vertex's root among them,   */
+/*   ascending by root index (-1: unreferenced); comp_of_face [F].  Waits for the stream (one read: the count and the status).        */
+/* vt_mesh_component_stats (asynchronous): per component n_faces, n_vertices [C] i32; bbox [C][2][3] (min, max) in the vertices' type;  */
+/*   area [C] f64 = sum 0.5 |(v1-v0) x (v2-v0)|; volume [C] f64 = sum v0.(v1 x v2) / 6.  Each face term is float64 on the exactly      */
+/*   widened coordinates, one rounding per operation; the sums are exact fixed-point accumulations by integer atomics (DESIGN.md,     */
+/*   "mesh_topo.hip"), rounded once at the end: equal bits from run to run.                                                           */
+/* vt_mesh_edge_stats (asynchronous): per component, over the undirected edges {a,b}, a != b: n_edges (distinct), n_boundary (one     */
+/*   incident face), n_nonmanifold (three or more), n_misoriented (two faces that run along it in one direction), each [C] i32, by a  */
+/*   hash table of vt_mesh_edge_stats_workspace_bytes(F) bytes, sized from F: it cannot fill.                                         */
+/* vt_mesh_filter: keep [C] u8 -> out_verts (capacity V), out_faces (capacity F): the kept components' vertices and re-indexed faces   */
+/*   in their original order; vertex_map [V] i32 (new index or -1); the two counts.  Waits for the stream (one read).                  */
+size_t vt_mesh_components_workspace_bytes(int64_t V, int64_t F);
+int vt_mesh_components(const int32_t *faces, int64_t F, int64_t V, int32_t *labels, int *rounds, void *workspace, size_t workspace_bytes, void *stream);
+size_t vt_mesh_component_table_workspace_bytes(int64_t V, int64_t F);
+int vt_mesh_component_table(const int32_t *faces, int64_t F, int64_t V, const int32_t *labels, int32_t *comp_of_vertex, int32_t *comp_of_face,
+                            int *n_components, void *workspace, size_t workspace_bytes, void *stream);
+size_t vt_mesh_component_stats_workspace_bytes(int64_t C);
+int vt_mesh_component_stats(const void *verts, int verts_f64, int64_t V, const int32_t *faces, int64_t F, const int32_t *comp_of_vertex,
+                            const int32_t *comp_of_face, int64_t C, int32_t *n_faces, int32_t *n_vertices, void *bbox, double *area, double *volume,
+                            void *workspace, size_t workspace_bytes, void *stream);
+size_t vt_mesh_edge_stats_workspace_bytes(int64_t F);
+int vt_mesh_edge_stats(const int32_t *faces, int64_t F, int64_t V, const int32_t *comp_of_vertex, int64_t C, int32_t *n_edges, int32_t *n_boundary,
+                       int32_t *n_nonmanifold, int32_t *n_misoriented, void *workspace, size_t workspace_bytes, void *stream);
+size_t vt_mesh_filter_workspace_bytes(int64_t V, int64_t F);
+int vt_mesh_filter(const void *verts, int verts_f64, int64_t V, const int32_t *faces, int64_t F, const int32_t *comp_of_vertex,
+                   const int32_t *comp_of_face, const uint8_t *keep, int64_t C, void *out_verts, int32_t *out_faces, int32_t *vertex_map,
+                   int *n_out_verts, int *n_out_faces, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,6 +156,7 @@ class TactileUnetGrads(ctypes.Structure):
 # name -> (restype, argtypes); kept in step with include/vtaco_hip.h (tests/test_abi.py
 # parses the header and checks that every declared symbol is exported and listed here)
 _VP, _I, _I64, _F, _D, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
+_IP = ctypes.POINTER(ctypes.c_int)
 SIGNATURES = {
     "vt_abi_version": (_I, []),
     "vt_last_error": (ctypes.c_char_p, []),
@@ -396,6 +397,16 @@ SIGNATURES = {
     "vt_icp_fit": (_I, [_VP, _VP, _I64, _I64, _VP, _I, _VP, _VP, _SZ, _VP]),                         # best_fit_transform, utils/icp.py:5-47
     "vt_icp_workspace_bytes": (_SZ, [_I64, _I64, _I]),
     "vt_icp": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _I, _D, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),       # icp, utils/icp.py:69-121
+    "vt_mesh_components_workspace_bytes": (_SZ, [_I64, _I64]),
+    "vt_mesh_components": (_I, [_VP, _I64, _I64, _VP, _IP, _VP, _SZ, _VP]),                           # trimesh graph.connected_components
+    "vt_mesh_component_table_workspace_bytes": (_SZ, [_I64, _I64]),
+    "vt_mesh_component_table": (_I, [_VP, _I64, _I64, _VP, _VP, _VP, _IP, _VP, _SZ, _VP]),
+    "vt_mesh_component_stats_workspace_bytes": (_SZ, [_I64]),
+    "vt_mesh_component_stats": (_I, [_VP, _I, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_mesh_edge_stats_workspace_bytes": (_SZ, [_I64]),
+    "vt_mesh_edge_stats": (_I, [_VP, _I64, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_mesh_filter_workspace_bytes": (_SZ, [_I64, _I64]),
+    "vt_mesh_filter": (_I, [_VP, _I, _I64, _VP, _I64, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _IP, _IP, _VP, _SZ, _VP]),
 }
 
 _lib = None

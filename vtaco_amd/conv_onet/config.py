@@ -67,7 +67,8 @@ def get_generator(model, cfg, device, **kwargs):
                        input_type=cfg['data']['input_type'], padding=cfg['data']['padding'],
                        with_img=cfg['model'].get('with_img', False), encode_t2d=cfg['model'].get('encoder_t2d', False),
                        reference_returns=kwargs.get('reference_returns', g.get('reference_returns', False)),
-                       extraction=g.get('extraction', 'dense'))
+                       extraction=g.get('extraction', 'dense'), components=g.get('components', 'all'),
+                       min_component_faces=g.get('min_component_faces', 0))
 
 
 def get_trainer(model, optimizer, cfg, device, **kwargs):

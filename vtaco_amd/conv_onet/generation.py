@@ -64,6 +64,27 @@ class Mesh(namedtuple("Mesh", ["vertices", "faces"])):
         with open(file_obj, "w") as fh:
             fh.write("\n".join(head + body) + "\n")
 
+    # what trimesh.Trimesh gives the reference's users for free (utils/mesh_clean.py, on the device)
+    def components(self):
+        """The MeshComponents record: labels, per-component counts, area, volume, Euler number, watertight, oriented."""
+        from ..utils import mesh_clean
+        return mesh_clean.components(self)
+
+    def split(self):
+        """One Mesh per connected component, in component order."""
+        from ..utils import mesh_clean
+        return mesh_clean.split(self)
+
+    def keep_largest(self, by="faces"):
+        """The largest component by 'faces', 'area' or 'volume'."""
+        from ..utils import mesh_clean
+        return mesh_clean.keep_largest(self, by=by)
+
+    def remove_small(self, min_faces=0, min_area_fraction=0.0):
+        """The components that reach both bounds."""
+        from ..utils import mesh_clean
+        return mesh_clean.remove_small(self, min_faces=min_faces, min_area_fraction=min_area_fraction)
+
 
 _tensor_version = operator.attrgetter("_version")
 
@@ -187,9 +208,20 @@ class Generator3D(object):
     lattice.  All three routes of generate_obj_mesh_wnf take it (visual: eager, not graph-captured; VTacOH and VTacO t2d: finger ids
     assigned at the query points), under the same range guard.  Refused (VtError): the attention decoder (TransformerFusion couples
     the points of a chunk: a sparse subset is not the dense field), a caller-supplied ``c_img_all`` (indexed by the dense lattice),
-    generate_obj_mesh_sharded and generate_mesh_graphed."""
+    generate_obj_mesh_sharded and generate_mesh_graphed.
+
+    ``components`` / ``min_component_faces``: the connected components of the finished object mesh that are returned -- ``"all"``
+    (the default), or the largest one by faces (``"largest"``), area (``"largest_area"``) or |signed volume| (``"largest_volume"``),
+    after the components with fewer than ``min_component_faces`` faces are dropped.  With the defaults nothing runs.  Otherwise the
+    filter (utils/mesh_clean.py) runs eagerly on the extracted mesh -- behind the graph replay where the route is graphed -- and costs
+    three host reads (the labels' convergence flags, the component count, the kept vertex and face counts; one more per two further
+    hooking rounds where hooks collided), in
+    generate_obj_mesh_wnf (all three routes, dense and MISE), generate_mesh_graphed and generate_obj_mesh_tactile, and
+    ``reference_returns`` measures the mesh that is returned.  Hand meshes and the Inferencer are left alone;
+    generate_obj_mesh_sharded refuses a non-default value (VtError)."""
 
     EXTRACTIONS = ("dense", "mise")
+    COMPONENTS = ("all", "largest", "largest_area", "largest_volume")
 
     MAX_SCENE_GRAPHS = 4
     FUSED_CHUNKS_PER_CALL = 256          # attention_local: chunks of points_batch_size points evaluated per launch sequence (see _fused_chunks_per_call)
@@ -200,7 +232,14 @@ class Generator3D(object):
                  resolution0=16, upsampling_steps=3, with_normals=False, padding=0.1, sample=False,
                  input_type=None, vol_info=None, vol_bound=None, simplify_nfaces=None, alpha=0.2,
                  with_img=False, encode_t2d=False, decode_precision="f16x3", depth_origin=None, reference_returns=False,
-                 extraction="dense"):
+                 extraction="dense", components="all", min_component_faces=0):
+        if components not in self.COMPONENTS:
+            raise VtError(f"Generator3D: components must be one of {self.COMPONENTS} (got {components!r})")
+        if int(min_component_faces) != min_component_faces or min_component_faces < 0:
+            raise VtError(f"Generator3D: min_component_faces must be an integer >= 0 (got {min_component_faces!r})")
+        # which connected components of the finished object mesh are returned (utils/mesh_clean.py): "all" with
+        # min_component_faces 0 -- the defaults -- returns the mesh as extracted and launches nothing
+        self.components, self.min_component_faces = components, int(min_component_faces)
         if extraction not in self.EXTRACTIONS:
             raise VtError(f"Generator3D: extraction must be one of {self.EXTRACTIONS} (got {extraction!r})")
         if extraction == "mise" and hasattr(getattr(model, "decoder", None), "fuser"):
@@ -474,8 +513,26 @@ class Generator3D(object):
         g["graph"].replay()
         return g["out"]
 
-    @_range_guarded
+    def _filters_components(self):
+        return self.components != "all" or self.min_component_faces > 0
+
+    def _clean(self, mesh):
+        """The returned components of a finished object mesh (``components``, ``min_component_faces``); the mesh itself with the defaults."""
+        if not self._filters_components() or mesh.faces.shape[0] == 0:
+            return mesh
+        from ..utils import mesh_clean
+        comps = mesh_clean.components(mesh)
+        keep = comps.n_faces >= self.min_component_faces
+        if self.components != "all":
+            keep = mesh_clean.largest_mask(comps, {"largest": "faces", "largest_area": "area", "largest_volume": "volume"}[self.components], among=keep)
+        return mesh_clean._filtered(mesh.vertices, mesh.faces, comps, keep)
+
     def generate_mesh_graphed(self, inputs):
+        """``_generate_mesh_graphed`` (the captured visual branch), then the component filter where one is set."""
+        return self._clean(self._generate_mesh_graphed(inputs))
+
+    @_range_guarded
+    def _generate_mesh_graphed(self, inputs):
         """Same result as ``generate_obj_mesh_wnf({'inputs': inputs})`` for the visual branch, with the
         ~110 launches of encode + decode + marching-cubes classification replayed as one hipGraph
         (launch-bound otherwise); only the data-dependent output sizing leaves the graph.  Safe across weight
@@ -494,8 +551,15 @@ class Generator3D(object):
         verts, faces, _ = ops.mc_emit(g["vol"], g["ws"], rescale=(nx / 2, (1 + self.padding) / nx), echo=g.get("echo"))
         return Mesh(verts, faces)
 
-    @_range_guarded(collective=True)
     def generate_obj_mesh_sharded(self, data, group=None):
+        """``_generate_obj_mesh_sharded``; a component filter is refused before anything is launched."""
+        if self._filters_components():
+            raise VtError("generate_obj_mesh_sharded: the component filter (components / min_component_faces) is not built for the sharded "
+                          "route; filter the returned mesh with Mesh.keep_largest / Mesh.remove_small")
+        return self._generate_obj_mesh_sharded(data, group)
+
+    @_range_guarded(collective=True)
+    def _generate_obj_mesh_sharded(self, data, group=None):
         """``generate_obj_mesh_wnf`` with the lattice split over the ranks of a process group (one process per GPU):
         every rank encodes the scene (cheap, deterministic: no broadcast), decodes its slab of x-plane pairs with no
         data-path collective, one all_gather of the logit slabs (8.4 MB at 128^3, 67 MB at 256^3) rebuilds the value
@@ -533,8 +597,12 @@ class Generator3D(object):
                                                       device=self.device)
         return self.extract_mesh(values.reshape(nx, nx, nx))
 
-    @_range_guarded
     def generate_obj_mesh_tactile(self, data, finger_feats, anchors, success, mode='within', radius=None, count=None):
+        """``_generate_obj_mesh_tactile``, then the component filter where one is set."""
+        return self._clean(self._generate_obj_mesh_tactile(data, finger_feats, anchors, success, mode=mode, radius=radius, count=count))
+
+    @_range_guarded
+    def _generate_obj_mesh_tactile(self, data, finger_feats, anchors, success, mode='within', radius=None, count=None):
         """Tactile branch of ``generate_obj_mesh_wnf`` (generation.py:159-257) without the dense
         ``c_img_all [1,nx^3,C]`` tensor and its CPU cdist glue: every lattice point gets the id of the finger whose
         contact points lie within ``radius`` (``mode='within'``, radius 0.015: VTacO, :245-255) or of the nearest
@@ -726,7 +794,7 @@ class Generator3D(object):
         """Encode -> dense decode -> marching cubes for one scene; ``data['inputs']`` is the
         point cloud [1,T,3].  Returns Mesh(vertices [V,3] f32, faces [F,3] i32) on the device -- or, with
         ``reference_returns``, (mesh, emd, cd) as the reference does (see reference_metrics)."""
-        mesh = self._generate_obj_mesh(data, c_img_all)
+        mesh = self._clean(self._generate_obj_mesh(data, c_img_all))
         if not self.reference_returns:
             return mesh
         emd, cd = self.reference_metrics(mesh, data)     # outside the range guard: the metrics are of the scene it kept
@@ -772,7 +840,7 @@ class Generator3D(object):
         if (not self.with_img and not self._plane_model() and not self._point_model() and self._graphs_allowed() and inputs.dim() == 3 and inputs.shape[0] == 1
                 and self._worth_capturing((tuple(inputs.shape), nx, self.decode_precision))):
             # the visual branch: the same launches replayed as one hipGraph per (cloud shape, lattice) -- 1.1 instead of 1.5 ms
-            return self.generate_mesh_graphed(inputs)
+            return self._generate_mesh_graphed(inputs)
         with torch.no_grad():
             c = self.model.encode_inputs(inputs)
             values = self.eval_lattice(c, nx, c_img_all=c_img_all if self.with_img else None)

@@ -1,0 +1,160 @@
+"""Topology of a triangle mesh (vt_mesh_components, vt_mesh_component_table, vt_mesh_component_stats, vt_mesh_edge_stats, vt_mesh_filter:
+csrc/mesh_topo.hip).  A submodule only: callers write ``ops.mesh.components``, ``ops.mesh.component_table``, ``ops.mesh.component_stats``,
+``ops.mesh.edge_stats``, ``ops.mesh.filter_components``.  faces are int32 [F,3] and vertices float32 or float64 [V,3] device tensors, as
+``ops.marching_cubes`` returns them; int64 faces are refused, not converted (a conversion would be a torch computation here: the caller
+writes ``faces.int()``).  F >= 1.  A face index outside [0, V) is found on the device by the calls that read a count back anyway
+(``components``, ``component_table``, ``filter_components``), which raise; no kernel dereferences such an index."""
+from collections import namedtuple
+import ctypes
+
+import torch
+
+from ._base import _lib, VtError, check, dev_ptr, stream_ptr, I32, U8, _c
+
+
+F64 = torch.float64
+ComponentTable = namedtuple("ComponentTable", ["n_components", "comp_of_vertex", "comp_of_face"])
+ComponentStats = namedtuple("ComponentStats", ["n_faces", "n_vertices", "bbox", "area", "volume"])
+EdgeStats = namedtuple("EdgeStats", ["n_edges", "n_boundary", "n_nonmanifold", "n_misoriented"])
+FilteredMesh = namedtuple("FilteredMesh", ["vertices", "faces", "vertex_map"])
+
+
+def _faces(what, faces, *others):
+    if not torch.is_tensor(faces) or any(not torch.is_tensor(t) for t in others):
+        raise VtError(f"{what}: expected tensors")
+    if not faces.is_cuda or any(t.device != faces.device for t in others):
+        raise VtError(f"{what}: every tensor must live on one HIP device (got {', '.join(str(t.device) for t in (faces,) + others)}); "
+                      "vtaco_amd has no CPU path")
+    if faces.dtype != I32:
+        raise VtError(f"{what}: faces must be int32, as ops.marching_cubes returns them (got {faces.dtype}); convert with faces.int()")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise VtError(f"{what}: faces must be [F,3] (got {tuple(faces.shape)})")
+    if faces.shape[0] < 1:
+        raise VtError(f"{what}: a mesh without faces has no components (F = 0)")
+    return _c(faces)
+
+
+def _count(what, n, name="V"):
+    if int(n) != n or int(n) < 1:
+        raise VtError(f"{what}: {name} must be an integer >= 1 (got {n})")
+    return int(n)
+
+
+def _vertices(what, vertices):
+    if vertices.dtype not in (torch.float32, F64):
+        raise VtError(f"{what}: vertices must be float32 or float64 (got {vertices.dtype})")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] < 1:
+        raise VtError(f"{what}: vertices must be [V,3] with V >= 1 (got {tuple(vertices.shape)})")
+    return _c(vertices)
+
+
+def _i32(what, t, n, name):
+    if t.dtype != I32 or tuple(t.shape) != (n,):
+        raise VtError(f"{what}: {name} must be int32 [{n}] (got {t.dtype} {tuple(t.shape)})")
+    return _c(t)
+
+
+def _ws(nbytes, dev):
+    return torch.empty((max(int(nbytes), 8) + 7) // 8, dtype=torch.int64, device=dev)
+
+
+def components(faces, n_vertices, return_rounds=False):
+    """labels int32 [V]: the smallest vertex index of each vertex's connected component (vt_mesh_components); an unreferenced vertex
+    keeps its own index.  Converged when it returns: the launcher repeats hooking rounds until one changes nothing, reading their flags
+    once per two rounds.  ``return_rounds``: (labels, rounds), rounds = the hooking rounds run, the one that changed nothing included."""
+    what = "mesh.components"
+    faces = _faces(what, faces)
+    V, F = _count(what, n_vertices), faces.shape[0]
+    labels = torch.empty(V, dtype=I32, device=faces.device)
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_components_workspace_bytes(V, F), faces.device)
+    rounds = ctypes.c_int(0)
+    check(lib.vt_mesh_components(dev_ptr(faces, "faces", I32), F, V, dev_ptr(labels, "labels", I32), ctypes.byref(rounds),
+                                 ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "vt_mesh_components")
+    return (labels, rounds.value) if return_rounds else labels
+
+
+def component_table(faces, labels):
+    """ComponentTable(n_components, comp_of_vertex int32 [V], comp_of_face int32 [F]) from ``components``' labels: components are
+    numbered by ascending root index over the roots that own a face; unreferenced vertices get -1 (vt_mesh_component_table)."""
+    what = "mesh.component_table"
+    faces = _faces(what, faces, labels)
+    if labels.dtype != I32 or labels.dim() != 1 or labels.shape[0] < 1:
+        raise VtError(f"{what}: labels must be int32 [V] (got {labels.dtype} {tuple(labels.shape)})")
+    labels = _c(labels)
+    V, F, dev = labels.shape[0], faces.shape[0], faces.device
+    cov = torch.empty(V, dtype=I32, device=dev)
+    cof = torch.empty(F, dtype=I32, device=dev)
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_component_table_workspace_bytes(V, F), dev)
+    n = ctypes.c_int(0)
+    check(lib.vt_mesh_component_table(dev_ptr(faces, "faces", I32), F, V, dev_ptr(labels, "labels", I32), dev_ptr(cov, "comp_of_vertex", I32),
+                                      dev_ptr(cof, "comp_of_face", I32), ctypes.byref(n), ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8,
+                                      stream_ptr()), "vt_mesh_component_table")
+    return ComponentTable(n.value, cov, cof)
+
+
+def component_stats(vertices, faces, table):
+    """ComponentStats(n_faces, n_vertices int32 [C], bbox [C,2,3] in the vertices' dtype, area, volume float64 [C]) per component of
+    ``table`` (vt_mesh_component_stats); nothing here waits for the device."""
+    what = "mesh.component_stats"
+    faces = _faces(what, faces, vertices, table.comp_of_vertex, table.comp_of_face)
+    vertices = _vertices(what, vertices)
+    V, F, C, dev = vertices.shape[0], faces.shape[0], _count(what, table.n_components, "n_components"), faces.device
+    cov, cof = _i32(what, table.comp_of_vertex, V, "comp_of_vertex"), _i32(what, table.comp_of_face, F, "comp_of_face")
+    nf = torch.empty(C, dtype=I32, device=dev)
+    nv = torch.empty(C, dtype=I32, device=dev)
+    bbox = torch.empty((C, 2, 3), dtype=vertices.dtype, device=dev)
+    area = torch.empty(C, dtype=F64, device=dev)
+    volume = torch.empty(C, dtype=F64, device=dev)
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_component_stats_workspace_bytes(C), dev)
+    check(lib.vt_mesh_component_stats(dev_ptr(vertices, "vertices", vertices.dtype), int(vertices.dtype == F64), V, dev_ptr(faces, "faces", I32), F,
+                                      dev_ptr(cov, "comp_of_vertex", I32), dev_ptr(cof, "comp_of_face", I32), C, dev_ptr(nf, "n_faces", I32),
+                                      dev_ptr(nv, "n_vertices", I32), dev_ptr(bbox, "bbox", bbox.dtype), dev_ptr(area, "area", F64),
+                                      dev_ptr(volume, "volume", F64), ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()),
+          "vt_mesh_component_stats")
+    return ComponentStats(nf, nv, bbox, area, volume)
+
+
+def edge_stats(faces, table):
+    """EdgeStats(n_edges, n_boundary, n_nonmanifold, n_misoriented), int32 [C] each, over the undirected edges of every component
+    (vt_mesh_edge_stats); nothing here waits for the device."""
+    what = "mesh.edge_stats"
+    faces = _faces(what, faces, table.comp_of_vertex)
+    cov = table.comp_of_vertex
+    if cov.dtype != I32 or cov.dim() != 1 or cov.shape[0] < 1:
+        raise VtError(f"{what}: comp_of_vertex must be int32 [V] (got {cov.dtype} {tuple(cov.shape)})")
+    cov = _c(cov)
+    V, F, C, dev = cov.shape[0], faces.shape[0], _count(what, table.n_components, "n_components"), faces.device
+    outs = [torch.empty(C, dtype=I32, device=dev) for _ in range(4)]
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_edge_stats_workspace_bytes(F), dev)
+    check(lib.vt_mesh_edge_stats(dev_ptr(faces, "faces", I32), F, V, dev_ptr(cov, "comp_of_vertex", I32), C, *[dev_ptr(t, "counts", I32) for t in outs],
+                                 ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "vt_mesh_edge_stats")
+    return EdgeStats(*outs)
+
+
+def filter_components(vertices, faces, table, keep):
+    """FilteredMesh(vertices, faces, vertex_map int32 [V]): the components with ``keep`` (uint8 or bool [C]) set -- their faces in the
+    original order, re-indexed, and the vertices those reference in the original order (vt_mesh_filter).  The outputs are slices of
+    capacity (V, F) buffers, cut after one read of the two counts; keeping nothing gives V = 0 and F = 0."""
+    what = "mesh.filter_components"
+    faces = _faces(what, faces, vertices, table.comp_of_vertex, table.comp_of_face, keep)
+    vertices = _vertices(what, vertices)
+    V, F, C, dev = vertices.shape[0], faces.shape[0], _count(what, table.n_components, "n_components"), faces.device
+    cov, cof = _i32(what, table.comp_of_vertex, V, "comp_of_vertex"), _i32(what, table.comp_of_face, F, "comp_of_face")
+    if keep.dtype not in (U8, torch.bool) or tuple(keep.shape) != (C,):
+        raise VtError(f"{what}: keep must be uint8 or bool [{C}] (got {keep.dtype} {tuple(keep.shape)})")
+    keep = _c(keep.view(U8) if keep.dtype == torch.bool else keep)
+    out_v = torch.empty((V, 3), dtype=vertices.dtype, device=dev)
+    out_f = torch.empty((F, 3), dtype=I32, device=dev)
+    vmap = torch.empty(V, dtype=I32, device=dev)
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_filter_workspace_bytes(V, F), dev)
+    nv, nf = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.vt_mesh_filter(dev_ptr(vertices, "vertices", vertices.dtype), int(vertices.dtype == F64), V, dev_ptr(faces, "faces", I32), F,
+                             dev_ptr(cov, "comp_of_vertex", I32), dev_ptr(cof, "comp_of_face", I32), dev_ptr(keep, "keep", U8), C,
+                             dev_ptr(out_v, "out_vertices", out_v.dtype), dev_ptr(out_f, "out_faces", I32), dev_ptr(vmap, "vertex_map", I32),
+                             ctypes.byref(nv), ctypes.byref(nf), ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "vt_mesh_filter")
+    return FilteredMesh(out_v[:nv.value], out_f[:nf.value], vmap)

@@ -1,0 +1,138 @@
+"""Which pieces a mesh consists of, which of them are closed, and the mesh without its floaters -- what the reference gets from wrapping
+its meshes in ``trimesh.Trimesh`` (``split``, ``area``, ``volume``, ``is_watertight``, ``euler_number``), on the device
+(csrc/mesh_topo.hip through ``ops.mesh``).
+
+    components(mesh) -> MeshComponents           every per-component tensor, on the device; ``.report()`` for a host dict
+    split(mesh) -> [Mesh, ...]                   one mesh per component, in component order
+    keep_largest(mesh, by='faces') -> Mesh       by 'faces', 'area' or 'volume' (|signed volume|); ties go to the lower component
+    remove_small(mesh, min_faces=0, min_area_fraction=0.0) -> Mesh
+
+A mesh is ``generation.Mesh``, any object with ``.vertices`` / ``.faces``, or a ``(vertices, faces)`` pair of device tensors: vertices
+float32 or float64 [V,3], faces int32 [F,3] (int64 faces are converted here).  Components are numbered by their smallest vertex index.
+Unreferenced vertices belong to no component and are dropped by every function that returns a mesh.  A mesh without faces has no
+components: ``split`` gives [], the other two give the empty mesh.  There is no host path."""
+from collections import namedtuple
+
+import torch
+
+from .._lib import VtError
+
+BY = ("faces", "area", "volume")
+
+_FIELDS = ["labels", "comp_of_vertex", "comp_of_face", "n_components", "n_faces", "n_vertices", "bbox", "area", "volume", "n_edges",
+           "n_boundary", "n_nonmanifold", "n_misoriented", "euler", "watertight", "oriented", "rounds"]
+
+
+class MeshComponents(namedtuple("MeshComponents", _FIELDS)):
+    """labels, comp_of_vertex [V] and comp_of_face [F] (int32), n_components (int), and per component: n_faces, n_vertices, n_edges,
+    n_boundary, n_nonmanifold, n_misoriented, euler (int32 [C]), bbox [C,2,3], area, volume (float64 [C]; the volume is signed, about
+    the origin, and means something for closed components only), watertight = no boundary and no non-manifold edge, oriented =
+    watertight with every edge run once in each direction (bool [C]).  ``rounds``: the hooking rounds the labels took."""
+    __slots__ = ()
+
+    def report(self):
+        """A host dict of lists, one entry per component (one device-to-host copy of the integer block, one of the float block)."""
+        ints = torch.stack([self.n_faces, self.n_vertices, self.n_edges, self.n_boundary, self.n_nonmanifold, self.n_misoriented,
+                            self.euler, self.watertight.int(), self.oriented.int()]).cpu().tolist() if self.n_components else [[]] * 9
+        flts = torch.stack([self.area, self.volume]).cpu().tolist() if self.n_components else [[]] * 2
+        names = ["n_faces", "n_vertices", "n_edges", "n_boundary", "n_nonmanifold", "n_misoriented", "euler"]
+        out = {"n_components": self.n_components, "rounds": self.rounds}
+        out.update(dict(zip(names, ints[:7])))
+        out["watertight"] = [bool(x) for x in ints[7]]
+        out["oriented"] = [bool(x) for x in ints[8]]
+        out["area"], out["volume"] = flts
+        return out
+
+
+def _parts(mesh):
+    if hasattr(mesh, "vertices") and hasattr(mesh, "faces"):
+        v, f = mesh.vertices, mesh.faces
+    else:
+        v, f = mesh
+    if not torch.is_tensor(v) or not torch.is_tensor(f) or not v.is_cuda or not f.is_cuda:
+        raise VtError("mesh_clean: vertices and faces must be tensors on a HIP device; vtaco_amd has no CPU path")
+    if f.dtype == torch.int64:
+        f = f.int()
+    return v, f
+
+
+def _empty(v, f):
+    from ..conv_onet.generation import Mesh
+    return Mesh(v[:0], f[:0])
+
+
+def components(mesh):
+    """The MeshComponents record of ``mesh``.  Two host reads: the labels' convergence flags (one read per two hooking rounds; a mesh
+    whose hooks did not collide takes two rounds) and the component count."""
+    from .. import ops
+    v, f = _parts(mesh)
+    if f.shape[0] == 0:
+        raise VtError("mesh_clean.components: a mesh without faces has no components (F = 0)")
+    m = ops.mesh
+    labels, rounds = m.components(f, v.shape[0], return_rounds=True)
+    table = m.component_table(f, labels)
+    st = m.component_stats(v, f, table)
+    ed = m.edge_stats(f, table)
+    euler = st.n_vertices - ed.n_edges + st.n_faces
+    watertight = (ed.n_boundary == 0) & (ed.n_nonmanifold == 0)
+    oriented = watertight & (ed.n_misoriented == 0)
+    return MeshComponents(labels, table.comp_of_vertex, table.comp_of_face, table.n_components, st.n_faces, st.n_vertices, st.bbox, st.area,
+                          st.volume, ed.n_edges, ed.n_boundary, ed.n_nonmanifold, ed.n_misoriented, euler, watertight, oriented, rounds)
+
+
+def _filtered(v, f, comps, keep):
+    from .. import ops
+    from ..conv_onet.generation import Mesh
+    table = ops.mesh.ComponentTable(comps.n_components, comps.comp_of_vertex, comps.comp_of_face)
+    out = ops.mesh.filter_components(v, f, table, keep)
+    return Mesh(out.vertices, out.faces)
+
+
+def split(mesh, comps=None):
+    """One Mesh per component, in component order (``comps``: a MeshComponents of this mesh, when the caller has one).  One filter
+    call per component: each scans all V vertices and F faces, allocates capacity (V, F) outputs and reads its two counts back, so the
+    cost is C host reads and C passes over the mesh -- meant for the handful of pieces a generated mesh has, not for thousands (use
+    ``comp_of_face`` / ``comp_of_vertex`` of ``components`` to bucket those)."""
+    v, f = _parts(mesh)
+    if f.shape[0] == 0:
+        return []
+    comps = components((v, f)) if comps is None else comps
+    eye = torch.eye(comps.n_components, dtype=torch.uint8, device=f.device)
+    return [_filtered(v, f, comps, eye[c]) for c in range(comps.n_components)]
+
+
+def largest_mask(comps, by="faces", among=None):
+    """bool [C]: the one component that is largest by ``by`` among those ``among`` (bool [C]; all without it) marks; equal sizes go to
+    the lower component; nothing set where ``among`` is empty.  Nothing is read back."""
+    if by not in BY:
+        raise VtError(f"keep_largest: by must be one of {BY} (got {by!r})")
+    size = {"faces": comps.n_faces, "area": comps.area, "volume": comps.volume.abs()}[by].double()
+    if among is not None:
+        size = torch.where(among, size, -1.0)                                # (sizes are >= 0: a component outside never wins)
+    # the first index of the maximum: argmax leaves the choice among equals open
+    idx = torch.arange(comps.n_components, device=size.device)
+    mask = idx == torch.where(size == size.max(), idx, comps.n_components).min()
+    return mask if among is None else mask & among
+
+
+def keep_largest(mesh, by="faces", comps=None):
+    """The component with the most faces, the largest area or the largest |signed volume|; equal sizes go to the lower component."""
+    if by not in BY:
+        raise VtError(f"keep_largest: by must be one of {BY} (got {by!r})")
+    v, f = _parts(mesh)
+    if f.shape[0] == 0:
+        return _empty(v, f)
+    comps = components((v, f)) if comps is None else comps
+    return _filtered(v, f, comps, largest_mask(comps, by))
+
+
+def remove_small(mesh, min_faces=0, min_area_fraction=0.0, comps=None):
+    """Every component with at least ``min_faces`` faces and at least ``min_area_fraction`` of the mesh's total area."""
+    if int(min_faces) != min_faces or min_faces < 0 or not 0.0 <= float(min_area_fraction) <= 1.0:
+        raise VtError(f"remove_small: min_faces must be an integer >= 0 and min_area_fraction lie in [0, 1] (got {min_faces}, {min_area_fraction})")
+    v, f = _parts(mesh)
+    if f.shape[0] == 0:
+        return _empty(v, f)
+    comps = components((v, f)) if comps is None else comps
+    keep = (comps.n_faces >= int(min_faces)) & (comps.area >= float(min_area_fraction) * comps.area.sum())
+    return _filtered(v, f, comps, keep)
