@@ -1548,6 +1548,40 @@ int vt_mesh_filter(const void *verts, int verts_f64, int64_t V, const int32_t *f
                    const int32_t *comp_of_face, const uint8_t *keep, int64_t C, void *out_verts, int32_t *out_faces, int32_t *vertex_map,
                    int *n_out_verts, int *n_out_faces, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- mesh simplification and welding (mesh_simplify.hip) --------------------------------------------------------------------------- */
+/* Replaces: the reference's generation.simplify_nfaces (simplify_mesh of its ConvONet tool chain) and trimesh's merge_vertices         */
+/*   (process=True).  Vertex clustering on a grid of `resolution` cells along the box's longest side, one vertex per occupied cell      */
+/*   placed by the summed quadric of the faces that touch it (Lindstrom 2000); tests/mesh_simplify_ref.py is the definition and the     */
+/*   kernels equal it bit for bit.  Topology is not preserved.  Meshes and size rules as in the block above.                            */
+/* state [32] i32, 8-byte aligned, owned by the caller and shared by the calls of one simplification: words 0..11 the bounding box of   */
+/*   the referenced vertices (six u64 images of doubles; it never leaves the device), 16 the status bits (1 a face index outside        */
+/*   [0, V), 2 a non-finite referenced coordinate, 4 K >= 2^21, 8 a weld key beyond int64, 16 a map that is not of these faces),        */
+/*   17 K, 18 the face count, 19 the placement's fallbacks.  vt_mesh_cluster / vt_mesh_weld initialise it.                              */
+/* vt_mesh_cluster (asynchronous): cluster_of_vertex [V] i32, the cluster of every referenced vertex (-1: unreferenced); clusters are   */
+/*   the occupied cells, numbered by ascending representative = the cell's lowest vertex index; cluster_rep (capacity V): the           */
+/*   representatives; K into state.  1 <= resolution <= 2^20.                                                                           */
+/* vt_mesh_weld (asynchronous): the same two maps with the key of merge_vertices: tol = 0 equal coordinates (-0.0 = +0.0, a vertex with */
+/*   a NaN merges with nothing), tol > 0 equal rint(x / tol) per axis.                                                                  */
+/* vt_mesh_cluster_faces: the faces on cluster ids, those with two equal ids dropped and, with `unique`, of the faces with one          */
+/*   unordered triple the lowest kept, in the original order, into out_faces (capacity F); out_faces = NULL counts only.  Waits for     */
+/*   the stream (one read of state: *n_clusters, *n_out_faces and the status bits, which make it VT_ERR_INVALID).                       */
+/* vt_mesh_cluster_place (asynchronous): out_verts [K][3] in the vertices' type: placement 0 the quadric minimiser about the cluster's  */
+/*   mean (eigenvalues <= 1e-3 of the largest dropped; outside the cell: the mean, counted in state word 19), 1 the mean, 2 the         */
+/*   representative's own coordinates (welding).  The sums are exact fixed-point accumulations by integer atomics.                     */
+size_t vt_mesh_cluster_workspace_bytes(int64_t V, int64_t F);
+int vt_mesh_cluster(const void *verts, int verts_f64, int64_t V, const int32_t *faces, int64_t F, int resolution, int32_t *cluster_of_vertex,
+                    int32_t *cluster_rep, int32_t *state, void *workspace, size_t workspace_bytes, void *stream);
+size_t vt_mesh_weld_workspace_bytes(int64_t V, int64_t F);
+int vt_mesh_weld(const void *verts, int verts_f64, int64_t V, const int32_t *faces, int64_t F, double tol, int32_t *cluster_of_vertex, int32_t *cluster_rep,
+                 int32_t *state, void *workspace, size_t workspace_bytes, void *stream);
+size_t vt_mesh_cluster_faces_workspace_bytes(int64_t F);
+int vt_mesh_cluster_faces(const int32_t *faces, int64_t F, int64_t V, const int32_t *cluster_of_vertex, int unique, int32_t *out_faces, int32_t *state,
+                          int *n_clusters, int *n_out_faces, void *workspace, size_t workspace_bytes, void *stream);
+size_t vt_mesh_cluster_place_workspace_bytes(int64_t K);
+int vt_mesh_cluster_place(const void *verts, int verts_f64, int64_t V, const int32_t *faces, int64_t F, int resolution, const int32_t *cluster_of_vertex,
+                          const int32_t *cluster_rep, int64_t K, int placement, void *out_verts, int32_t *state, void *workspace, size_t workspace_bytes,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -407,6 +407,14 @@ SIGNATURES = {
     "vt_mesh_edge_stats": (_I, [_VP, _I64, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "vt_mesh_filter_workspace_bytes": (_SZ, [_I64, _I64]),
     "vt_mesh_filter": (_I, [_VP, _I, _I64, _VP, _I64, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _IP, _IP, _VP, _SZ, _VP]),
+    "vt_mesh_cluster_workspace_bytes": (_SZ, [_I64, _I64]),
+    "vt_mesh_cluster": (_I, [_VP, _I, _I64, _VP, _I64, _I, _VP, _VP, _VP, _VP, _SZ, _VP]),              # generation.simplify_nfaces
+    "vt_mesh_weld_workspace_bytes": (_SZ, [_I64, _I64]),
+    "vt_mesh_weld": (_I, [_VP, _I, _I64, _VP, _I64, _D, _VP, _VP, _VP, _VP, _SZ, _VP]),                 # trimesh merge_vertices
+    "vt_mesh_cluster_faces_workspace_bytes": (_SZ, [_I64]),
+    "vt_mesh_cluster_faces": (_I, [_VP, _I64, _I64, _VP, _I, _VP, _VP, _IP, _IP, _VP, _SZ, _VP]),
+    "vt_mesh_cluster_place_workspace_bytes": (_SZ, [_I64]),
+    "vt_mesh_cluster_place": (_I, [_VP, _I, _I64, _VP, _I64, _I, _VP, _VP, _I64, _I, _VP, _VP, _VP, _SZ, _VP]),
 }
 
 _lib = None

@@ -12,6 +12,7 @@ encoder + MANO layer on the device and the reference's wrist-frame post-processi
 """
 from __future__ import annotations
 
+import numbers
 import operator
 import os
 from collections import namedtuple
@@ -84,6 +85,22 @@ class Mesh(namedtuple("Mesh", ["vertices", "faces"])):
         """The components that reach both bounds."""
         from ..utils import mesh_clean
         return mesh_clean.remove_small(self, min_faces=min_faces, min_area_fraction=min_area_fraction)
+
+    def simplify(self, nfaces=None, resolution=None, placement="quadric"):
+        """At most ``nfaces`` faces, or the clustering at ``resolution`` cells: vertex clustering with quadric placement.  Topology is
+        not preserved."""
+        from ..utils import mesh_clean
+        return mesh_clean.simplify(self, nfaces=nfaces, resolution=resolution, placement=placement)
+
+    def simplify_report(self, nfaces=None, resolution=None, placement="quadric"):
+        """(mesh, report): ``simplify`` and the resolution it used, the probes of its search, the clusters and the fallbacks."""
+        from ..utils import mesh_clean
+        return mesh_clean.simplify_report(self, nfaces=nfaces, resolution=resolution, placement=placement)
+
+    def merge_vertices(self, tol=0.0, unique_faces=False):
+        """Equal vertices merged (within ``tol`` of a lattice where ``tol`` > 0), collapsed faces and unreferenced vertices dropped."""
+        from ..utils import mesh_clean
+        return mesh_clean.merge_vertices(self, tol=tol, unique_faces=unique_faces)
 
 
 _tensor_version = operator.attrgetter("_version")
@@ -218,7 +235,14 @@ class Generator3D(object):
     hooking rounds where hooks collided), in
     generate_obj_mesh_wnf (all three routes, dense and MISE), generate_mesh_graphed and generate_obj_mesh_tactile, and
     ``reference_returns`` measures the mesh that is returned.  Hand meshes and the Inferencer are left alone;
-    generate_obj_mesh_sharded refuses a non-default value (VtError)."""
+    generate_obj_mesh_sharded refuses a non-default value (VtError).
+
+    ``simplify_nfaces`` (config ``generation.simplify_nfaces``): a positive integer N simplifies the finished object mesh to at most N
+    faces -- ``Mesh.simplify(nfaces=N)``, vertex clustering with quadric placement (utils/mesh_clean.py, csrc/mesh_simplify.hip) --
+    after the component filter, in the same places as that filter; everything downstream, ``reference_returns``' EMD and Chamfer
+    included, sees the simplified mesh.  It costs one host read per probe of the search for the grid (some ten).  The result has at
+    most N faces but is not the finest such grid, and its topology is not the input's (``Mesh.components()`` reports what it is).
+    ``None`` (the default) launches nothing.  The Inferencer does not apply it; generate_obj_mesh_sharded refuses it (VtError)."""
 
     EXTRACTIONS = ("dense", "mise")
     COMPONENTS = ("all", "largest", "largest_area", "largest_volume")
@@ -240,6 +264,9 @@ class Generator3D(object):
         # which connected components of the finished object mesh are returned (utils/mesh_clean.py): "all" with
         # min_component_faces 0 -- the defaults -- returns the mesh as extracted and launches nothing
         self.components, self.min_component_faces = components, int(min_component_faces)
+        if simplify_nfaces is not None and (isinstance(simplify_nfaces, bool) or not isinstance(simplify_nfaces, numbers.Integral)
+                                            or simplify_nfaces < 1):
+            raise VtError(f"Generator3D: simplify_nfaces must be a positive integer or None (got {simplify_nfaces!r})")
         if extraction not in self.EXTRACTIONS:
             raise VtError(f"Generator3D: extraction must be one of {self.EXTRACTIONS} (got {extraction!r})")
         if extraction == "mise" and hasattr(getattr(model, "decoder", None), "fuser"):
@@ -262,7 +289,7 @@ class Generator3D(object):
         self.device = device
         self.resolution0, self.upsampling_steps = resolution0, upsampling_steps
         self.with_normals, self.input_type, self.padding, self.sample = with_normals, input_type, padding, sample
-        self.simplify_nfaces, self.alpha = simplify_nfaces, alpha
+        self.simplify_nfaces, self.alpha = None if simplify_nfaces is None else int(simplify_nfaces), alpha
         self.with_img, self.encode_t2d = with_img, encode_t2d
         # the tactile sensor's flat depth reading [240*320] (the VTacO branch compares every depth image with it): an array, a
         # path, or None = the reference's ./data/VTacO_mesh/depth_origin.txt (generation.py:17), read when first needed
@@ -517,7 +544,15 @@ class Generator3D(object):
         return self.components != "all" or self.min_component_faces > 0
 
     def _clean(self, mesh):
-        """The returned components of a finished object mesh (``components``, ``min_component_faces``); the mesh itself with the defaults."""
+        """The returned components of a finished object mesh (``components``, ``min_component_faces``), then simplified to
+        ``simplify_nfaces`` faces; the mesh itself with the defaults."""
+        mesh = self._kept_components(mesh)
+        if self.simplify_nfaces is None or mesh.faces.shape[0] <= self.simplify_nfaces:
+            return mesh
+        from ..utils import mesh_clean
+        return mesh_clean.simplify(mesh, nfaces=self.simplify_nfaces)
+
+    def _kept_components(self, mesh):
         if not self._filters_components() or mesh.faces.shape[0] == 0:
             return mesh
         from ..utils import mesh_clean
@@ -552,7 +587,10 @@ class Generator3D(object):
         return Mesh(verts, faces)
 
     def generate_obj_mesh_sharded(self, data, group=None):
-        """``_generate_obj_mesh_sharded``; a component filter is refused before anything is launched."""
+        """``_generate_obj_mesh_sharded``; a component filter or ``simplify_nfaces`` is refused before anything is launched."""
+        if self.simplify_nfaces is not None:
+            raise VtError("generate_obj_mesh_sharded: simplify_nfaces is not built for the sharded route; simplify the returned mesh with "
+                          "Mesh.simplify(nfaces=...)")
         if self._filters_components():
             raise VtError("generate_obj_mesh_sharded: the component filter (components / min_component_faces) is not built for the sharded "
                           "route; filter the returned mesh with Mesh.keep_largest / Mesh.remove_small")

@@ -10,7 +10,8 @@ This file only re-exports: callers write ``ops.name`` and look the name up at ca
 ``ops.planes.sample_planes``, ``ops.voxel_encoder.encode_grid``, ``ops.points.point_sample``, ``ops.voxelize.surface``.
 ``ops.metrics`` is re-exported by the names of its ``__all__``; its closest-point launchers are reached as ``ops.metrics.closest_point_mesh``.
 ``icp`` is a submodule only as well: ``ops.icp.nn_points``, ``ops.icp.icp_fit``, ``ops.icp.icp``; so is ``mesh``: ``ops.mesh.components``,
-``ops.mesh.component_table``, ``ops.mesh.component_stats``, ``ops.mesh.edge_stats``, ``ops.mesh.filter_components``.
+``ops.mesh.component_table``, ``ops.mesh.component_stats``, ``ops.mesh.edge_stats``, ``ops.mesh.filter_components``, and for simplification and welding ``ops.mesh.cluster``, ``ops.mesh.weld``,
+``ops.mesh.cluster_faces``, ``ops.mesh.cluster_place``.
 """
 from . import (_base, decode, decode_train, decode_wide, fusion, icp, labels, mano, mc, mesh, metrics, mise, nets2d, planes, pointnet, points, resnet_train, touch,  # noqa: F401
                unet3d, voxel, voxel_encoder, voxelize)

@@ -1,5 +1,6 @@
 """Topology of a triangle mesh (vt_mesh_components, vt_mesh_component_table, vt_mesh_component_stats, vt_mesh_edge_stats, vt_mesh_filter:
-csrc/mesh_topo.hip).  A submodule only: callers write ``ops.mesh.components``, ``ops.mesh.component_table``, ``ops.mesh.component_stats``,
+csrc/mesh_topo.hip) and, at the end of the file, its simplification and welding (vt_mesh_cluster, vt_mesh_weld, vt_mesh_cluster_faces,
+vt_mesh_cluster_place: csrc/mesh_simplify.hip).  A submodule only: callers write ``ops.mesh.components``, ``ops.mesh.component_table``, ``ops.mesh.component_stats``,
 ``ops.mesh.edge_stats``, ``ops.mesh.filter_components``.  faces are int32 [F,3] and vertices float32 or float64 [V,3] device tensors, as
 ``ops.marching_cubes`` returns them; int64 faces are refused, not converted (a conversion would be a torch computation here: the caller
 writes ``faces.int()``).  F >= 1.  A face index outside [0, V) is found on the device by the calls that read a count back anyway
@@ -158,3 +159,98 @@ def filter_components(vertices, faces, table, keep):
                              dev_ptr(out_v, "out_vertices", out_v.dtype), dev_ptr(out_f, "out_faces", I32), dev_ptr(vmap, "vertex_map", I32),
                              ctypes.byref(nv), ctypes.byref(nf), ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "vt_mesh_filter")
     return FilteredMesh(out_v[:nv.value], out_f[:nf.value], vmap)
+
+
+# ---- simplification and welding (csrc/mesh_simplify.hip) ---------------------------------------------------------------------------------
+# ``cluster`` / ``weld`` make the vertex map, ``cluster_faces`` the faces on it (the one call that waits for the device),
+# ``cluster_place`` the vertices.  The calls of one simplification share a ``state`` tensor (int32 [32]: the bounding box as it stays on
+# the device, the status bits, K, the face count, the fallbacks); utils/mesh_clean.py strings them together.
+Clusters = namedtuple("Clusters", ["cluster_of_vertex", "cluster_rep", "state", "resolution"])
+ClusterFaces = namedtuple("ClusterFaces", ["n_clusters", "n_faces", "faces"])
+MAX_RESOLUTION = 1 << 20
+MAX_CLUSTERS = 1 << 21
+PLACEMENTS = ("quadric", "mean", "representative")
+STATE_BAD, STATE_K, STATE_NF, STATE_FALLBACKS = 16, 17, 18, 19
+
+
+def _cluster_call(what, fn_name, vertices, faces, arg):
+    faces = _faces(what, faces, vertices)
+    vertices = _vertices(what, vertices)
+    V, F, dev = vertices.shape[0], faces.shape[0], faces.device
+    cov = torch.empty(V, dtype=I32, device=dev)
+    rep = torch.empty(V, dtype=I32, device=dev)
+    state = torch.empty(32, dtype=I32, device=dev)
+    lib = _lib.load()
+    ws = _ws(getattr(lib, fn_name + "_workspace_bytes")(V, F), dev)
+    check(getattr(lib, fn_name)(dev_ptr(vertices, "vertices", vertices.dtype), int(vertices.dtype == F64), V, dev_ptr(faces, "faces", I32), F, arg,
+                                dev_ptr(cov, "cluster_of_vertex", I32), dev_ptr(rep, "cluster_rep", I32), dev_ptr(state, "state", I32),
+                                ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), fn_name)
+    return cov, rep, state
+
+
+def cluster(vertices, faces, resolution):
+    """Clusters(cluster_of_vertex int32 [V], cluster_rep int32 [V] of which the first K count, state, resolution): the referenced vertices
+    grouped by their cell of a grid with ``resolution`` cells along the longest side of their bounding box (vt_mesh_cluster).  Nothing
+    here waits for the device: K, and the status bit of a face index outside [0, V) or of a non-finite vertex, are words 17 and 16 of
+    ``state``; ``cluster_faces`` reads them."""
+    what = "mesh.cluster"
+    if isinstance(resolution, bool) or int(resolution) != resolution or not 1 <= int(resolution) <= MAX_RESOLUTION:
+        raise VtError(f"{what}: resolution must be an integer in [1, {MAX_RESOLUTION}] (got {resolution!r})")
+    cov, rep, state = _cluster_call(what, "vt_mesh_cluster", vertices, faces, int(resolution))
+    return Clusters(cov, rep, state, int(resolution))
+
+
+def weld(vertices, faces, tol=0.0):
+    """Clusters of equal vertices (vt_mesh_weld): ``tol`` 0 equal coordinates (-0.0 equals +0.0; a vertex with a NaN merges with
+    nothing), ``tol`` > 0 equal rint(x / tol) per axis.  Asynchronous like ``cluster``."""
+    what = "mesh.weld"
+    tol = float(tol)
+    if not 0.0 <= tol < float("inf"):
+        raise VtError(f"{what}: tol must be finite and >= 0 (got {tol})")
+    cov, rep, state = _cluster_call(what, "vt_mesh_weld", vertices, faces, tol)
+    return Clusters(cov, rep, state, 1)
+
+
+def cluster_faces(faces, clusters, unique=True, count_only=False):
+    """ClusterFaces(n_clusters, n_faces, faces int32 [n_faces,3] or None with ``count_only``): the faces on cluster ids without those
+    that collapsed and, with ``unique``, without later copies of an unordered triple, in the original order (vt_mesh_cluster_faces).
+    One read of ``state``; its status bits raise here."""
+    what = "mesh.cluster_faces"
+    cov, state = clusters.cluster_of_vertex, clusters.state
+    faces = _faces(what, faces, cov, state)
+    V, F, dev = cov.shape[0], faces.shape[0], faces.device
+    cov = _i32(what, cov, V, "cluster_of_vertex")
+    state = _i32(what, state, 32, "state")
+    out = None if count_only else torch.empty((F, 3), dtype=I32, device=dev)
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_cluster_faces_workspace_bytes(F), dev)
+    nk, nf = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.vt_mesh_cluster_faces(dev_ptr(faces, "faces", I32), F, V, dev_ptr(cov, "cluster_of_vertex", I32), int(bool(unique)),
+                                    dev_ptr(out, "out_faces", I32), dev_ptr(state, "state", I32), ctypes.byref(nk), ctypes.byref(nf),
+                                    ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "vt_mesh_cluster_faces")
+    return ClusterFaces(nk.value, nf.value, None if count_only else out[:nf.value])
+
+
+def cluster_place(vertices, faces, clusters, n_clusters, placement="quadric"):
+    """vertices [K,3] of the clusters, in the input's dtype (vt_mesh_cluster_place): ``'quadric'`` the minimiser of the summed quadric
+    about the cluster's mean, the mean itself where that leaves the cell (counted in word 19 of ``state``); ``'mean'``;
+    ``'representative'`` the representative's own coordinates.  Nothing here waits for the device."""
+    what = "mesh.cluster_place"
+    if placement not in PLACEMENTS:
+        raise VtError(f"{what}: placement must be one of {PLACEMENTS} (got {placement!r})")
+    cov, rep, state = clusters.cluster_of_vertex, clusters.cluster_rep, clusters.state
+    faces = _faces(what, faces, vertices, cov, rep, state)
+    vertices = _vertices(what, vertices)
+    V, F, dev = vertices.shape[0], faces.shape[0], faces.device
+    K = _count(what, n_clusters, "n_clusters")
+    if K > V:
+        raise VtError(f"{what}: n_clusters must be at most V (got {K} > {V})")
+    cov, rep, state = _i32(what, cov, V, "cluster_of_vertex"), _i32(what, rep, V, "cluster_rep"), _i32(what, state, 32, "state")
+    out = torch.empty((K, 3), dtype=vertices.dtype, device=dev)
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_cluster_place_workspace_bytes(K), dev)
+    check(lib.vt_mesh_cluster_place(dev_ptr(vertices, "vertices", vertices.dtype), int(vertices.dtype == F64), V, dev_ptr(faces, "faces", I32), F,
+                                    clusters.resolution, dev_ptr(cov, "cluster_of_vertex", I32), dev_ptr(rep, "cluster_rep", I32), K,
+                                    PLACEMENTS.index(placement), dev_ptr(out, "out_vertices", out.dtype), dev_ptr(state, "state", I32),
+                                    ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "vt_mesh_cluster_place")
+    return out

@@ -6,6 +6,9 @@ its meshes in ``trimesh.Trimesh`` (``split``, ``area``, ``volume``, ``is_waterti
     split(mesh) -> [Mesh, ...]                   one mesh per component, in component order
     keep_largest(mesh, by='faces') -> Mesh       by 'faces', 'area' or 'volume' (|signed volume|); ties go to the lower component
     remove_small(mesh, min_faces=0, min_area_fraction=0.0) -> Mesh
+    simplify(mesh, nfaces=None, resolution=None, placement='quadric') -> Mesh        (csrc/mesh_simplify.hip, as the next two)
+    simplify_report(...) -> (Mesh, SimplifyReport)
+    merge_vertices(mesh, tol=0.0, unique_faces=False) -> Mesh
 
 A mesh is ``generation.Mesh``, any object with ``.vertices`` / ``.faces``, or a ``(vertices, faces)`` pair of device tensors: vertices
 float32 or float64 [V,3], faces int32 [F,3] (int64 faces are converted here).  Components are numbered by their smallest vertex index.
@@ -136,3 +139,97 @@ def remove_small(mesh, min_faces=0, min_area_fraction=0.0, comps=None):
     comps = components((v, f)) if comps is None else comps
     keep = (comps.n_faces >= int(min_faces)) & (comps.area >= float(min_area_fraction) * comps.area.sum())
     return _filtered(v, f, comps, keep)
+
+
+# ---- simplification and welding (csrc/mesh_simplify.hip; tests/mesh_simplify_ref.py is the definition) --------------------------------
+SimplifyReport = namedtuple("SimplifyReport", ["resolution", "probes", "n_clusters", "fallbacks", "cluster_of_vertex"])
+SimplifyReport.__doc__ = """resolution: the grid that was used (None: the mesh was returned unchanged); probes: the grids the search for
+``nfaces`` counted faces at; n_clusters: K, the vertices of the result; fallbacks: the clusters placed at their mean because the quadric's
+minimiser left the cell; cluster_of_vertex int32 [V]: the output vertex of every input vertex (-1: unreferenced)."""
+
+
+def _positive_int(what, name, x):
+    if isinstance(x, bool) or int(x) != x or int(x) < 1:
+        raise VtError(f"{what}: {name} must be a positive integer (got {x!r})")
+    return int(x)
+
+
+def _search(count, nfaces, max_resolution):
+    """(resolution, probes): gallop from (1, 2) while count(hi) <= nfaces, then bisect on the same predicate; the answer is lo.  count
+    is not monotone in the resolution (the lattice aliases): the answer has at most nfaces faces, it is not the finest such grid."""
+    lo, hi, probes = 1, 2, 0
+    while hi <= max_resolution:
+        probes += 1
+        if count(hi) > nfaces:
+            break
+        lo, hi = hi, 2 * hi
+    hi = min(hi, max_resolution + 1)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        probes += 1
+        if count(mid) <= nfaces:
+            lo = mid
+        else:
+            hi = mid
+    return lo, probes
+
+
+def simplify_report(mesh, nfaces=None, resolution=None, placement="quadric", _count_fallbacks=True):
+    """(Mesh, SimplifyReport).  Vertex clustering (Lindstrom 2000): the referenced vertices are grouped by their cell of a grid with
+    ``resolution`` cells along the longest side of their bounding box, every occupied cell becomes one vertex, faces that collapse and
+    later copies of a face are dropped, the rest keep their order and orientation.  ``placement='quadric'`` puts the vertex where the
+    summed squared distances to the planes of the cluster's faces (area-weighted) are smallest, within the cell; ``'mean'`` at the
+    mean of the cluster's vertices.  Exactly one of ``nfaces`` / ``resolution``: ``nfaces`` searches the grid (gallop, then bisection;
+    one host read per probe; probes run no placement) for a result of at most ``nfaces`` faces and returns the mesh itself, with
+    nothing launched, when it has no more than that.  Topology is NOT preserved: handles close, sheets that share a cell merge and
+    the result may have non-manifold edges (``components()`` reports them).  Deterministic, bit for bit."""
+    from .. import ops
+    from ..conv_onet.generation import Mesh
+    what = "mesh_clean.simplify"
+    if (nfaces is None) == (resolution is None):
+        raise VtError(f"{what}: give exactly one of nfaces / resolution (got nfaces={nfaces!r}, resolution={resolution!r})")
+    if placement not in ("quadric", "mean"):
+        raise VtError(f"{what}: placement must be 'quadric' or 'mean' (got {placement!r})")
+    v, f = _parts(mesh)
+    m = ops.mesh
+    probes = 0
+    if nfaces is not None:
+        nfaces = _positive_int(what, "nfaces", nfaces)
+        if f.shape[0] <= nfaces:
+            return (mesh if isinstance(mesh, Mesh) else Mesh(v, f)), SimplifyReport(None, 0, None, 0, None)
+        resolution, probes = _search(lambda r: m.cluster_faces(f, m.cluster(v, f, r), count_only=True).n_faces, nfaces, m.MAX_RESOLUTION)
+    elif isinstance(resolution, bool) or int(resolution) != resolution or not 1 <= int(resolution) <= m.MAX_RESOLUTION:
+        raise VtError(f"{what}: resolution must be an integer in [1, {m.MAX_RESOLUTION}] (got {resolution!r})")
+    if f.shape[0] == 0:
+        return _empty(v, f), SimplifyReport(int(resolution), 0, 0, 0, None)
+    clusters = m.cluster(v, f, int(resolution))
+    faces = m.cluster_faces(f, clusters)
+    if faces.n_clusters == 0:                                             # (no face with three valid indices is an error before this)
+        return _empty(v, f), SimplifyReport(int(resolution), probes, 0, 0, clusters.cluster_of_vertex)
+    vertices = m.cluster_place(v, f, clusters, faces.n_clusters, placement)
+    fallbacks = int(clusters.state[m.STATE_FALLBACKS]) if placement == "quadric" and _count_fallbacks else 0
+    return Mesh(vertices, faces.faces), SimplifyReport(int(resolution), probes, faces.n_clusters, fallbacks, clusters.cluster_of_vertex)
+
+
+def simplify(mesh, nfaces=None, resolution=None, placement="quadric"):
+    """``simplify_report`` without the report, and without its read of the fallback count."""
+    return simplify_report(mesh, nfaces=nfaces, resolution=resolution, placement=placement, _count_fallbacks=False)[0]
+
+
+def merge_vertices(mesh, tol=0.0, unique_faces=False):
+    """The mesh with equal vertices merged, as trimesh's ``merge_vertices`` / ``process=True`` leaves it: ``tol`` 0 merges equal
+    coordinates (-0.0 equals +0.0; a vertex with a NaN coordinate merges with nothing), ``tol`` > 0 the vertices with equal
+    rint(x / tol) on every axis.  Of each group the lowest vertex index survives with its own coordinates, the survivors keep their
+    order; faces with two equal corners are dropped, later copies of a face (as an unordered triple) with ``unique_faces``;
+    unreferenced vertices are dropped.  One host read."""
+    from .. import ops
+    from ..conv_onet.generation import Mesh
+    v, f = _parts(mesh)
+    if f.shape[0] == 0:
+        return _empty(v, f)
+    m = ops.mesh
+    clusters = m.weld(v, f, tol)
+    faces = m.cluster_faces(f, clusters, unique=bool(unique_faces))
+    if faces.n_clusters == 0:
+        return _empty(v, f)
+    return Mesh(m.cluster_place(v, f, clusters, faces.n_clusters, "representative"), faces.faces)
