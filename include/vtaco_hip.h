@@ -1582,6 +1582,39 @@ int vt_mesh_cluster_place(const void *verts, int verts_f64, int64_t V, const int
                           const int32_t *cluster_rep, int64_t K, int placement, void *out_verts, int32_t *state, void *workspace, size_t workspace_bytes,
                           void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------ */
+/* Fast winding number (csrc/winding_fast.hip; DESIGN.md section "winding_fast.hip"; tests/winding_fast_ref.py restates it in numpy):     */
+/* an octree over the faces' centroids, `depth` levels below the root (1 .. VT_WN_MAX_DEPTH), whose occupied cells carry the dipole       */
+/* expansion of their faces to order 2 (Barill et al. 2018).  Replaces: igl.fast_winding_number_for_meshes(V, F, Q) of the reference     */
+/* (src/conv_onet/training.py:307, 359, 723, 862), which vt_winding_number evaluates exactly.                                            */
+/* verts [V,3] f32, faces [F,3] i32 (indices clamped to [0, V) as vt_winding_number clamps them), pts [N,3] f32.                          */
+/* A tree is built by two asynchronous calls with one host read between them:                                                            */
+/*   vt_winding_tree_count  frame, leaf codes, the index pyramids and the list offsets, into the workspace                                 */
+/*                          (vt_winding_tree_workspace_bytes(V, F, depth) bytes, 0 for sizes outside the limits).  Its first 16 int32      */
+/*                          are the state the caller reads back: word 0 the status (bit 0: a vertex coordinate that is not finite),        */
+/*                          words 1 .. 8 the occupied cells of level 0 .. 7.                                                              */
+/*   vt_winding_tree_layout host only: from those 16 words, offsets[0..4] = the byte offsets in the tree of the pyramids (int32, level l   */
+/*                          at word (8^l - 1) / 7), the records (36 doubles per occupied cell, level by level: p[3], r, N0[3], M1[3][3],  */
+/*                          M2[6][3], area, faces), the list offsets (leaves + 1 int32), the lists (F int32, ascending inside a leaf)     */
+/*                          and the faces' corners in list order (F x 9 f32); offsets[5] = the tree's bytes.                              */
+/*   vt_winding_tree_build  the lists and every record, into `tree`; the same workspace, untouched since the count.  state_host[0] != 0   */
+/*                          (a bounding box that is not finite) is VT_ERR_INVALID.  The workspace is free afterwards.                      */
+/* vt_winding_tree_query (asynchronous, reads nothing back, safe to capture): out [N] f32, or f64 with out_f64; stats NULL or [N][2]     */
+/*   int32 (cells accepted, faces summed exactly).  A cell is accepted when |q - p|^2 > accuracy^2 r^2; order 0, 1 or 2.                  */
+/* Errors, all before any launch: a NULL array or a negative size is VT_ERR_INVALID; depth outside [1, VT_WN_MAX_DEPTH], F or V beyond    */
+/*   the mesh kernels' limits VT_ERR_UNSUPPORTED; a short workspace or tree VT_ERR_WORKSPACE.  F == 0 gives zeros, N == 0 launches        */
+/*   nothing.  Trees and results are bit-reproducible: no float atomic, one summation order.                                              */
+#define VT_WN_MAX_DEPTH 7
+int vt_winding_tree_default_depth(int64_t F);
+size_t vt_winding_tree_workspace_bytes(int64_t V, int64_t F, int depth);
+int vt_winding_tree_count(const float *verts, int64_t V, const int32_t *faces, int64_t F, int depth, void *workspace, size_t workspace_bytes,
+                          void *stream);
+int vt_winding_tree_layout(int64_t F, int depth, const int32_t *state_host, size_t *offsets);
+int vt_winding_tree_build(const float *verts, int64_t V, const int32_t *faces, int64_t F, int depth, const int32_t *state_host, void *workspace,
+                          size_t workspace_bytes, void *tree, size_t tree_bytes, void *stream);
+int vt_winding_tree_query(const void *tree, size_t tree_bytes, int64_t F, int depth, const int32_t *state_host, const float *pts, int64_t N,
+                          double accuracy, int order, void *out, int out_f64, int32_t *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -415,6 +415,12 @@ SIGNATURES = {
     "vt_mesh_cluster_faces": (_I, [_VP, _I64, _I64, _VP, _I, _VP, _VP, _IP, _IP, _VP, _SZ, _VP]),
     "vt_mesh_cluster_place_workspace_bytes": (_SZ, [_I64]),
     "vt_mesh_cluster_place": (_I, [_VP, _I, _I64, _VP, _I64, _I, _VP, _VP, _I64, _I, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_winding_tree_default_depth": (_I, [_I64]),
+    "vt_winding_tree_workspace_bytes": (_SZ, [_I64, _I64, _I]),
+    "vt_winding_tree_count": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _SZ, _VP]),
+    "vt_winding_tree_layout": (_I, [_I64, _I, _VP, _VP]),
+    "vt_winding_tree_build": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _VP, _SZ, _VP, _SZ, _VP]),
+    "vt_winding_tree_query": (_I, [_VP, _SZ, _I64, _I, _VP, _VP, _I64, _D, _I, _VP, _I, _VP, _VP]),   # igl.fast_winding_number_for_meshes
 }
 
 _lib = None

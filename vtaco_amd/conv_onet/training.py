@@ -188,10 +188,34 @@ class Trainer:
             hit = cache[name] = (m['v'], m['f'], v, f)
         return hit[2], hit[3]
 
+    def _device_tree(self, vf_dict, name):
+        """The winding-number tree (``ops.winding.build``) of ``vf_dict[name]``, built once per mesh object beside ``_device_mesh``'s
+        upload and rebuilt when that is replaced (VTACO_WINDING=fast)."""
+        from .. import ops
+        v, f = self._device_mesh(vf_dict, name)
+        cache = self.__dict__.setdefault("_tree_cache", {})
+        hit = cache.get(name)
+        if hit is None or hit[0] is not v or hit[1] is not f:
+            if len(cache) >= 4096:
+                cache.pop(next(iter(cache)))
+            hit = cache[name] = (v, f, ops.winding.build(v, f))
+        return hit[2]
+
+    def _scene_winding(self, vf_dict, names, pts):
+        """Winding numbers [B, N] of pts [B, N, 3] against the scenes' meshes.  VTACO_WINDING unset or ``exact``: the exact sum in one
+        launch (vt_winding_number_scenes); ``fast``: the cached trees' hierarchical approximation, accuracy 2 and order 2 as the
+        reference's libigl call (vt_winding_tree_query)."""
+        from .. import ops
+        mode = os.environ.get("VTACO_WINDING", "exact") or "exact"
+        if mode == "exact":
+            return ops.winding_number_scenes([self._device_mesh(vf_dict, n) for n in names], pts)    # one launch
+        if mode != "fast":
+            raise VtError(f"VTACO_WINDING must be 'exact' or 'fast' (got '{mode}')")
+        return ops.winding.query_scenes([self._device_tree(vf_dict, n) for n in names], pts.float().contiguous())
+
     def _t2d_samples(self, data, vf_dict, normalise_depth):
         """Query points, finger per row and winding-number targets of a VTacO step (training.py:809-866 / 672-733), plus the t2d
         net's outputs and the depth images as the calling variant uses them."""
-        from .. import ops
         from ..common import contact_clouds_from_depth
         dev = self.device
         p = data.get('points')                                        # only its shape and a host view are used here
@@ -246,7 +270,7 @@ class Trainer:
                 p_sample[b, k:] = p_host[b][np.random.randint(N, size=S - k)]
             p_sample_t = torch.from_numpy(p_sample).to(dev)
         names = data.get('points.name')
-        occ_new = ops.winding_number_scenes([self._device_mesh(vf_dict, names[b]) for b in range(B)], p_sample_t)    # one launch
+        occ_new = self._scene_winding(vf_dict, [names[b] for b in range(B)], p_sample_t)
         cam_info = torch.cat((cam_pos.reshape(B, -1), cam_rot.reshape(B, -1)), dim=1).to(dev).float()
         return {'inputs': inputs, 'imgs': imgs, 'p_sample': p_sample_t, 'finger': torch.from_numpy(finger).to(dev), 'occ': occ_new,
                 'pred_depth': pred_depth, 'digit': c_hand_d['mano_param'], 'depths': depths, 'cam_info': cam_info}
@@ -452,8 +476,10 @@ class Trainer:
         chamfer = chamfer_distance_device(pc_hand.contiguous(), pc_pred.contiguous())
         verts = hand_in_object_frame(pc_pred.cpu().numpy(), mano_gt.cpu().numpy()[:, :3], data.get('points.wrist').cpu().numpy(), pc_ply)
         scales = [np.max(np.sqrt(np.sum(pc_ply[b] ** 2, axis=1))) for b in range(B)]
+        fast = (os.environ.get("VTACO_WINDING", "exact") or "exact") == "fast"
         depth = penetration_depth_scenes(torch.from_numpy(verts.astype(np.float32)).to(dev),
-                                         [self._device_mesh(vf_dict, names[b]) for b in range(B)], scales)
+                                         [self._device_mesh(vf_dict, names[b]) for b in range(B)], scales, winding='fast' if fast else 'exact',
+                                         trees=[self._device_tree(vf_dict, names[b]) for b in range(B)] if fast else None)
         return {'chamfer_distance': float(chamfer.double().mean()),
                 'hand_joints_error': float(np.mean(hand_joint_error(joints_gt, joints_pred))),
                 'penetration_depth': float(np.mean(depth))}

@@ -107,36 +107,54 @@ def _inside_depth(d2, winding):
     return dist.max(dim=-1)[0]
 
 
-def signed_distance(pts, verts, faces):
+def _winding(winding, verts, faces, pts):
+    """The winding numbers of pts by the exact kernel or by the tree of ``ops.winding`` (built for this call)."""
+    from . import ops
+    if winding == 'exact':
+        return ops.winding_number(verts, faces, pts)
+    if winding == 'fast':
+        return ops.winding.fast(verts, faces, pts)
+    raise ValueError("winding must be 'exact' or 'fast'")
+
+
+def signed_distance(pts, verts, faces, winding='exact'):
     """Distance from every query point pts [N,3] to the mesh (verts [V,3] f32, faces [F,3] int; device tensors), float64 [N]: the square
     root of vt_closest_point_mesh's minimum, negative where the winding number (vt_winding_number) exceeds 0.5 -- inside a closed,
-    outward-oriented mesh."""
+    outward-oriented mesh.  ``winding='fast'`` takes the sign from the hierarchical approximation (vt_winding_tree_query) instead."""
     from . import ops
     pts = pts.float()
     d2 = ops.metrics.closest_point_mesh(verts.float(), faces, pts, want_point=False).d2
-    inside = ops.winding_number(verts, faces, pts) > 0.5
+    inside = _winding(winding, verts, faces, pts) > 0.5
     dist = torch.sqrt(d2)
     return torch.where(inside, -dist, dist)
 
 
-def penetration_depth(hand_verts, verts, faces, scale):
+def penetration_depth(hand_verts, verts, faces, scale, winding='exact'):
     """Penetration depth of a hand into an object mesh as the reference's eval_step measures it (training.py:406-419): 0 when no hand
     vertex has a winding number above 0.5; otherwise the largest distance to the surface (trimesh.proximity.closest_point there,
     vt_closest_point_mesh here) among the vertices that have, times ``scale`` -- the reference passes max ||pc_ply|| of the uncentred
-    object cloud.  hand_verts [K,3] in the mesh's frame, verts [V,3] f32, faces [F,3] int on the device -> float."""
+    object cloud.  hand_verts [K,3] in the mesh's frame, verts [V,3] f32, faces [F,3] int on the device -> float.  ``winding``: 'exact'
+    (vt_winding_number) or 'fast' (vt_winding_tree_query)."""
     from . import ops
     pts = hand_verts.float()
     d2 = ops.metrics.closest_point_mesh(verts.float(), faces, pts, want_point=False).d2
-    return float(_inside_depth(d2, ops.winding_number(verts, faces, pts))) * float(scale)
+    return float(_inside_depth(d2, _winding(winding, verts, faces, pts))) * float(scale)
 
 
-def penetration_depth_scenes(hand_verts, meshes, scales):
+def penetration_depth_scenes(hand_verts, meshes, scales, winding='exact', trees=None):
     """``penetration_depth`` for a batch in one launch sequence each (vt_closest_point_mesh_scenes, vt_winding_number_scenes):
-    hand_verts [B,K,3] on the device, meshes = [(verts f32 [V,3], faces i32 [F,3])] per scene, scales [B] -> float64 array [B]."""
+    hand_verts [B,K,3] on the device, meshes = [(verts f32 [V,3], faces i32 [F,3])] per scene, scales [B] -> float64 array [B].
+    ``winding='fast'`` queries one tree per scene (``trees``: those of ``ops.winding.build``, built here when not given)."""
     from . import ops
     pts = hand_verts.float().contiguous()
     d2 = ops.metrics.closest_point_mesh_scenes(meshes, pts, want_point=False).d2
-    depth = _inside_depth(d2, ops.winding_number_scenes(meshes, pts))
+    if winding == 'exact':
+        w = ops.winding_number_scenes(meshes, pts)
+    elif winding == 'fast':
+        w = ops.winding.query_scenes(trees if trees is not None else [ops.winding.build(v, f) for v, f in meshes], pts)
+    else:
+        raise ValueError("winding must be 'exact' or 'fast'")
+    depth = _inside_depth(d2, w)
     return depth.cpu().numpy() * np.asarray(scales, dtype=np.float64)
 
 

@@ -11,10 +11,11 @@ This file only re-exports: callers write ``ops.name`` and look the name up at ca
 ``ops.metrics`` is re-exported by the names of its ``__all__``; its closest-point launchers are reached as ``ops.metrics.closest_point_mesh``.
 ``icp`` is a submodule only as well: ``ops.icp.nn_points``, ``ops.icp.icp_fit``, ``ops.icp.icp``; so is ``mesh``: ``ops.mesh.components``,
 ``ops.mesh.component_table``, ``ops.mesh.component_stats``, ``ops.mesh.edge_stats``, ``ops.mesh.filter_components``, and for simplification and welding ``ops.mesh.cluster``, ``ops.mesh.weld``,
-``ops.mesh.cluster_faces``, ``ops.mesh.cluster_place``.
+``ops.mesh.cluster_faces``, ``ops.mesh.cluster_place``.  ``winding`` is a submodule only too: ``ops.winding.build``, ``ops.winding.query``,
+``ops.winding.fast``, ``ops.winding.query_scenes`` (the exact sum stays ``ops.winding_number``).
 """
 from . import (_base, decode, decode_train, decode_wide, fusion, icp, labels, mano, mc, mesh, metrics, mise, nets2d, planes, pointnet, points, resnet_train, touch,  # noqa: F401
-               unet3d, voxel, voxel_encoder, voxelize)
+               unet3d, voxel, voxel_encoder, voxelize, winding)
 from ._base import *            # noqa: F401,F403
 from ._base import _c, _lib, _ptr_array     # noqa: F401
 from .decode import *           # noqa: F401,F403

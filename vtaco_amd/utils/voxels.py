@@ -63,7 +63,11 @@ def _interior(v, f, res, loc, scale, rule="parity"):
         if f.shape[0] == 0:
             return torch.zeros((res,) * 3, dtype=torch.bool, device=v.device)
         return ops.winding_number(v, f, _centres(int(res), loc, scale, v.device)) > 0.5
-    raise ValueError("rule must be 'parity' or 'winding'")
+    if rule == "fast_winding":
+        if f.shape[0] == 0:
+            return torch.zeros((res,) * 3, dtype=torch.bool, device=v.device)
+        return ops.winding.fast(v, f, _centres(int(res), loc, scale, v.device)) > 0.5
+    raise ValueError("rule must be 'parity', 'winding' or 'fast_winding'")
 
 
 def _ray(v, f, res, loc, scale):
@@ -96,7 +100,10 @@ def voxelize_surface(mesh, resolution):
 def voxelize_interior(mesh, resolution, rule='parity'):
     """bool [resolution]^3: the voxel centres inside the mesh (unit frame).  ``'parity'``: crossings of the +z ray, exact for a
     watertight mesh; ``'winding'``: the generalized winding number > 0.5 (``ops.winding_number``, O(voxels x faces)), the robust choice
-    for meshes that are not watertight."""
+    for meshes that are not watertight; ``'fast_winding'``: the same test on the hierarchical approximation (``ops.winding.fast``: an
+    octree of dipole expansions, accuracy 2, order 2; a few hundred cell or face terms per voxel instead of every face).  The tree is
+    built per call.  Measured at 64^3 (README, "winding_fast.hip"): 11.4 ms against 1463 ms on a 976 125-face mesh, 4.5 against 7.2 ms at
+    4 096 faces; below about 2 500 faces ``'winding'`` is the quicker rule."""
     return _interior(*_mesh_tensors(mesh), resolution, *_UNIT, rule=rule)
 
 
