@@ -1615,6 +1615,28 @@ int vt_winding_tree_build(const float *verts, int64_t V, const int32_t *faces, i
 int vt_winding_tree_query(const void *tree, size_t tree_bytes, int64_t F, int depth, const int32_t *state_host, const float *pts, int64_t N,
                           double accuracy, int order, void *out, int out_f64, int32_t *stats, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------ */
+/* Closest point on a mesh through that octree (csrc/closest_point_tree.hip; DESIGN.md section "closest_point_tree.hip";                  */
+/* tests/closest_point_tree_ref.py restates it in numpy): the d2, face and closest of vt_closest_point_mesh, bit for bit -- both call     */
+/* one cp_face (csrc/closest_point_face.h) -- from a walk that skips every cell whose bounding box is farther than the best face so far.  */
+/* `tree`, `depth` and `state_host` are a built winding tree's (vt_winding_tree_build) and the 16 words its caller read back.             */
+/*   vt_closest_tree_layout host only: offsets[0..1] = the byte offsets in the side buffer of the boxes (6 doubles lo[3], hi[3] per       */
+/*                          occupied cell, level by level as the tree's records) and of the face records (14 doubles per face, in list    */
+/*                          order: slot t is face lists[t]); offsets[2] = the side buffer's bytes.  Its first int32 is the status word    */
+/*                          (bit 0: a face index outside [0, V); that face is in no box and is never read).                              */
+/*   vt_closest_tree_build  the boxes and the records, into `side`, from the tree and the mesh it was built on.                           */
+/*   vt_closest_tree_query  d2 [N] f64, face [N] i32, closest NULL or [N][3] f64, stats NULL or [N][2] int32 (boxes tested, faces        */
+/*                          tested).  A cell is skipped when lb - delta > best, delta = 2^-40 S^2 (S from the frame and the query).       */
+/*                          VTACO_CLOSEST_TREE_WALK = plain | seed | order | seed+order (the default) picks the walk: equal results.      */
+/* Both launch functions are asynchronous, read nothing back and allocate nothing.  Errors, all before any launch: a NULL array, F <= 0   */
+/*   or V <= 0 is VT_ERR_INVALID (a mesh needs vertices and faces, as for vt_closest_point_mesh); depth outside [1, VT_WN_MAX_DEPTH]      */
+/*   VT_ERR_UNSUPPORTED; a short tree or side buffer VT_ERR_WORKSPACE.  N == 0 launches nothing.                                          */
+int vt_closest_tree_layout(int64_t F, int depth, const int32_t *state_host, size_t *offsets);
+int vt_closest_tree_build(const float *verts, int64_t V, const int32_t *faces, int64_t F, int depth, const int32_t *state_host, const void *tree,
+                          size_t tree_bytes, void *side, size_t side_bytes, void *stream);
+int vt_closest_tree_query(const void *tree, size_t tree_bytes, const void *side, size_t side_bytes, int64_t F, int depth, const int32_t *state_host,
+                          const float *pts, int64_t N, double *d2, int32_t *face, double *closest, int32_t *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

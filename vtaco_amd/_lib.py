@@ -421,6 +421,9 @@ SIGNATURES = {
     "vt_winding_tree_layout": (_I, [_I64, _I, _VP, _VP]),
     "vt_winding_tree_build": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _VP, _SZ, _VP, _SZ, _VP]),
     "vt_winding_tree_query": (_I, [_VP, _SZ, _I64, _I, _VP, _VP, _I64, _D, _I, _VP, _I, _VP, _VP]),   # igl.fast_winding_number_for_meshes
+    "vt_closest_tree_layout": (_I, [_I64, _I, _VP, _VP]),
+    "vt_closest_tree_build": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _VP, _SZ, _VP, _SZ, _VP]),
+    "vt_closest_tree_query": (_I, [_VP, _SZ, _VP, _SZ, _I64, _I, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP]),   # trimesh.proximity.closest_point
 }
 
 _lib = None

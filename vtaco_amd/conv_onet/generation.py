@@ -102,6 +102,11 @@ class Mesh(namedtuple("Mesh", ["vertices", "faces"])):
         from ..utils import mesh_clean
         return mesh_clean.merge_vertices(self, tol=tol, unique_faces=unique_faces)
 
+    def signed_distance_field(self, resolution, loc=None, scale=None, winding='fast', distance='tree'):
+        """float64 [resolution]^3: the signed distance to this mesh at the voxel centres of ``VoxelGrid``'s lattice (utils/voxels.py)."""
+        from ..utils import voxels
+        return voxels.signed_distance_field(self, resolution, loc=loc, scale=scale, winding=winding, distance=distance)
+
 
 _tensor_version = operator.attrgetter("_version")
 

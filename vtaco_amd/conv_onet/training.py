@@ -201,6 +201,20 @@ class Trainer:
             hit = cache[name] = (v, f, ops.winding.build(v, f))
         return hit[2]
 
+    def _device_closest_tree(self, vf_dict, name):
+        """The closest-point tree (``ops.metrics.closest_point_tree_build``) of ``vf_dict[name]``, on the cached winding tree of
+        ``_device_tree`` and cached beside it, rebuilt when that is (VTACO_CLOSEST_POINT=tree)."""
+        from .. import ops
+        v, f = self._device_mesh(vf_dict, name)
+        tree = self._device_tree(vf_dict, name)
+        cache = self.__dict__.setdefault("_closest_tree_cache", {})
+        hit = cache.get(name)
+        if hit is None or hit[0] is not tree:
+            if len(cache) >= 4096:
+                cache.pop(next(iter(cache)))
+            hit = cache[name] = (tree, ops.metrics.closest_point_tree_build(v, f, tree=tree))
+        return hit[1]
+
     def _scene_winding(self, vf_dict, names, pts):
         """Winding numbers [B, N] of pts [B, N, 3] against the scenes' meshes.  VTACO_WINDING unset or ``exact``: the exact sum in one
         launch (vt_winding_number_scenes); ``fast``: the cached trees' hierarchical approximation, accuracy 2 and order 2 as the
@@ -451,7 +465,8 @@ class Trainer:
         the reference's eval_step (training.py:163-166, 393-419): the naive Chamfer of ``points.pc_hand`` against the predicted MANO
         vertices (vt_chamfer_nn), the joint error against the MANO layer on the ground-truth pose, and the penetration depth of the
         predicted hand, moved to the object's frame, into the scene's ground-truth mesh (vt_winding_number_scenes,
-        vt_closest_point_mesh_scenes), scaled by max ||pc_ply||."""
+        vt_closest_point_mesh_scenes), scaled by max ||pc_ply||.  VTACO_CLOSEST_POINT unset or ``brute``: that launch; ``tree``: a walk
+        of each scene's cached face octree (vt_closest_tree_query: equal bits)."""
         from ..common import hand_in_object_frame
         from ..eval import chamfer_distance_device, hand_joint_error, penetration_depth_scenes
         dev = self.device
@@ -477,9 +492,13 @@ class Trainer:
         verts = hand_in_object_frame(pc_pred.cpu().numpy(), mano_gt.cpu().numpy()[:, :3], data.get('points.wrist').cpu().numpy(), pc_ply)
         scales = [np.max(np.sqrt(np.sum(pc_ply[b] ** 2, axis=1))) for b in range(B)]
         fast = (os.environ.get("VTACO_WINDING", "exact") or "exact") == "fast"
+        closest = os.environ.get("VTACO_CLOSEST_POINT", "brute") or "brute"
+        if closest not in ("brute", "tree"):
+            raise VtError(f"VTACO_CLOSEST_POINT must be 'brute' or 'tree' (got '{closest}')")
         depth = penetration_depth_scenes(torch.from_numpy(verts.astype(np.float32)).to(dev),
                                          [self._device_mesh(vf_dict, names[b]) for b in range(B)], scales, winding='fast' if fast else 'exact',
-                                         trees=[self._device_tree(vf_dict, names[b]) for b in range(B)] if fast else None)
+                                         trees=[self._device_tree(vf_dict, names[b]) for b in range(B)] if fast else None, distance=closest,
+                                         ctrees=[self._device_closest_tree(vf_dict, names[b]) for b in range(B)] if closest == "tree" else None)
         return {'chamfer_distance': float(chamfer.double().mean()),
                 'hand_joints_error': float(np.mean(hand_joint_error(joints_gt, joints_pred))),
                 'penetration_depth': float(np.mean(depth))}

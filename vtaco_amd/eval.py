@@ -117,37 +117,67 @@ def _winding(winding, verts, faces, pts):
     raise ValueError("winding must be 'exact' or 'fast'")
 
 
-def signed_distance(pts, verts, faces, winding='exact'):
+def _distance2(distance, verts, faces, pts, tree=None):
+    """vt_closest_point_mesh's d2 of pts [N,3] by the brute-force kernel or through the face octree (built for this call, on ``tree`` when
+    one is given): equal bits."""
+    from . import ops
+    if distance == 'brute':
+        return ops.metrics.closest_point_mesh(verts.float(), faces, pts, want_point=False).d2
+    if distance == 'tree':
+        return ops.metrics.closest_point_tree_query(ops.metrics.closest_point_tree_build(verts.float(), faces, tree=tree), pts, want_point=False).d2
+    raise ValueError("distance must be 'brute' or 'tree'")
+
+
+def signed_distance(pts, verts, faces, winding='exact', distance='brute'):
     """Distance from every query point pts [N,3] to the mesh (verts [V,3] f32, faces [F,3] int; device tensors), float64 [N]: the square
     root of vt_closest_point_mesh's minimum, negative where the winding number (vt_winding_number) exceeds 0.5 -- inside a closed,
-    outward-oriented mesh.  ``winding='fast'`` takes the sign from the hierarchical approximation (vt_winding_tree_query) instead."""
+    outward-oriented mesh.  ``winding='fast'`` takes the sign from the hierarchical approximation (vt_winding_tree_query) instead.
+    ``distance='tree'`` finds the same minimum by walking the face octree (vt_closest_tree_query: equal bits); with ``winding='fast'``
+    one octree serves both halves."""
     from . import ops
-    pts = pts.float()
-    d2 = ops.metrics.closest_point_mesh(verts.float(), faces, pts, want_point=False).d2
+    pts = pts.float().contiguous()
+    if winding == 'fast' and distance == 'tree':
+        tree = ops.winding.build(verts.float(), faces)
+        d2 = _distance2(distance, verts, faces, pts, tree=tree)
+        inside = ops.winding.query(tree, pts) > 0.5
+        dist = torch.sqrt(d2)
+        return torch.where(inside, -dist, dist)
+    d2 = _distance2(distance, verts, faces, pts)
     inside = _winding(winding, verts, faces, pts) > 0.5
     dist = torch.sqrt(d2)
     return torch.where(inside, -dist, dist)
 
 
-def penetration_depth(hand_verts, verts, faces, scale, winding='exact'):
+def penetration_depth(hand_verts, verts, faces, scale, winding='exact', distance='brute'):
     """Penetration depth of a hand into an object mesh as the reference's eval_step measures it (training.py:406-419): 0 when no hand
     vertex has a winding number above 0.5; otherwise the largest distance to the surface (trimesh.proximity.closest_point there,
     vt_closest_point_mesh here) among the vertices that have, times ``scale`` -- the reference passes max ||pc_ply|| of the uncentred
     object cloud.  hand_verts [K,3] in the mesh's frame, verts [V,3] f32, faces [F,3] int on the device -> float.  ``winding``: 'exact'
-    (vt_winding_number) or 'fast' (vt_winding_tree_query)."""
-    from . import ops
-    pts = hand_verts.float()
-    d2 = ops.metrics.closest_point_mesh(verts.float(), faces, pts, want_point=False).d2
+    (vt_winding_number) or 'fast' (vt_winding_tree_query); ``distance``: 'brute' (vt_closest_point_mesh) or 'tree' (vt_closest_tree_query:
+    equal bits)."""
+    pts = hand_verts.float().contiguous()
+    d2 = _distance2(distance, verts, faces, pts)
     return float(_inside_depth(d2, _winding(winding, verts, faces, pts))) * float(scale)
 
 
-def penetration_depth_scenes(hand_verts, meshes, scales, winding='exact', trees=None):
+def penetration_depth_scenes(hand_verts, meshes, scales, winding='exact', trees=None, distance='brute', ctrees=None):
     """``penetration_depth`` for a batch in one launch sequence each (vt_closest_point_mesh_scenes, vt_winding_number_scenes):
     hand_verts [B,K,3] on the device, meshes = [(verts f32 [V,3], faces i32 [F,3])] per scene, scales [B] -> float64 array [B].
-    ``winding='fast'`` queries one tree per scene (``trees``: those of ``ops.winding.build``, built here when not given)."""
+    ``winding='fast'`` queries one tree per scene (``trees``: those of ``ops.winding.build``, built here when not given).
+    ``distance='tree'`` walks one face octree per scene (``ctrees``: those of ``ops.metrics.closest_point_tree_build``, built here -- on
+    ``trees`` where given -- when not): equal bits."""
     from . import ops
     pts = hand_verts.float().contiguous()
-    d2 = ops.metrics.closest_point_mesh_scenes(meshes, pts, want_point=False).d2
+    if distance == 'brute':
+        d2 = ops.metrics.closest_point_mesh_scenes(meshes, pts, want_point=False).d2
+    elif distance == 'tree':
+        if ctrees is None:
+            ctrees = [ops.metrics.closest_point_tree_build(v, f, tree=None if trees is None else trees[b]) for b, (v, f) in enumerate(meshes)]
+        if winding == 'fast' and trees is None:
+            trees = [c.tree for c in ctrees]
+        d2 = ops.metrics.closest_point_tree_query_scenes(ctrees, pts, want_point=False).d2
+    else:
+        raise ValueError("distance must be 'brute' or 'tree'")
     if winding == 'exact':
         w = ops.winding_number_scenes(meshes, pts)
     elif winding == 'fast':
@@ -174,31 +204,32 @@ def sample_mesh_surface(verts, faces, n, generator=None):
     return (a[face] * w0 + b[face] * w1 + c[face] * w2).float(), face
 
 
-def mesh_distances(pred_mesh, gt_mesh, n, generator=None, threshold=0.01):
+def mesh_distances(pred_mesh, gt_mesh, n, generator=None, threshold=0.01, distance='brute'):
     """Surface-to-surface distances of two meshes, each (verts [V,3] f32, faces [F,3] int) on the device: ``n`` area-weighted samples
     per mesh (``sample_mesh_surface``), every sample's distance to the OTHER mesh's surface (vt_closest_point_mesh) -- not to its
     vertices, so a dense mesh is not favoured.  Returns floats: 'accuracy' (mean distance of the predicted samples to the ground-truth
     mesh), 'completeness' (the other way), 'chamfer_l1' (their mean), 'f_score' (harmonic mean of the shares of samples within
-    ``threshold``, precision and recall; 0 when both are 0)."""
-    from . import ops
+    ``threshold``, precision and recall; 0 when both are 0).  ``distance='tree'`` takes the same distances from a walk of each mesh's face
+    octree (vt_closest_tree_query: equal bits, far fewer faces per sample on a large mesh)."""
     (pv, pf), (gv, gf) = pred_mesh, gt_mesh
     sp, _ = sample_mesh_surface(pv, pf, n, generator)
     sg, _ = sample_mesh_surface(gv, gf, n, generator)
-    acc = torch.sqrt(ops.metrics.closest_point_mesh(gv.float(), gf, sp, want_point=False).d2)
-    comp = torch.sqrt(ops.metrics.closest_point_mesh(pv.float(), pf, sg, want_point=False).d2)
+    acc = torch.sqrt(_distance2(distance, gv, gf, sp))
+    comp = torch.sqrt(_distance2(distance, pv, pf, sg))
     precision, recall = float((acc <= threshold).double().mean()), float((comp <= threshold).double().mean())
     accuracy, completeness = float(acc.mean()), float(comp.mean())
     f_score = 2 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
     return {'accuracy': accuracy, 'completeness': completeness, 'chamfer_l1': 0.5 * (accuracy + completeness), 'f_score': f_score}
 
 
-def mesh_distances_aligned(pred_mesh, gt_mesh, n, generator=None, threshold=0.01, max_iterations=20, tolerance=1e-3):
+def mesh_distances_aligned(pred_mesh, gt_mesh, n, generator=None, threshold=0.01, max_iterations=20, tolerance=1e-3, distance='brute'):
     """``mesh_distances`` after a rigid registration of the predicted mesh onto the ground truth, so that a pose offset of the prediction
     does not read as shape error.  Both surfaces are sampled exactly as ``mesh_distances`` samples them; ``ops.icp.icp`` maps the
     predicted samples onto the ground-truth samples (vt_icp, float64); its T moves the predicted vertices, per component
     ((T00 x + T01 y) + T02 z) + T03 in float64, rounded to float32.  Returns ``mesh_distances`` of the moved mesh against the ground truth
     from the same random draws (the generator is put back to where the sampling began, so it ends where one ``mesh_distances`` call
-    leaves it), plus 'transform' (4x4 float64 numpy array) and 'icp_iterations' (int, the 0-based index of the last executed iteration)."""
+    leaves it), plus 'transform' (4x4 float64 numpy array) and 'icp_iterations' (int, the 0-based index of the last executed iteration).
+    ``distance`` is ``mesh_distances``'."""
     from . import ops
     (pv, pf), (gv, gf) = pred_mesh, gt_mesh
     state = generator.get_state() if generator is not None else torch.cuda.get_rng_state(pv.device)
@@ -211,7 +242,7 @@ def mesh_distances_aligned(pred_mesh, gt_mesh, n, generator=None, threshold=0.01
         generator.set_state(state)
     else:
         torch.cuda.set_rng_state(state, pv.device)
-    out = mesh_distances((moved, pf), gt_mesh, n, generator, threshold)
+    out = mesh_distances((moved, pf), gt_mesh, n, generator, threshold, distance=distance)
     out['transform'] = T.cpu().numpy()
     out['icp_iterations'] = int(fit.iterations)
     return out

@@ -1,5 +1,6 @@
-"""Evaluation metrics (vt_chamfer_nn, vt_emd_auction, vt_closest_point_mesh).  ``from .metrics import *`` hands the package the names of
-``__all__``; the closest-point launchers are reached through the submodule: ``ops.metrics.closest_point_mesh``."""
+"""Evaluation metrics (vt_chamfer_nn, vt_emd_auction, vt_closest_point_mesh, vt_closest_tree_*).  ``from .metrics import *`` hands the
+package the names of ``__all__``; the closest-point launchers are reached through the submodule: ``ops.metrics.closest_point_mesh``,
+``ops.metrics.closest_point_tree_build`` / ``closest_point_tree_query``."""
 from collections import namedtuple
 import ctypes
 
@@ -96,12 +97,8 @@ def closest_point_slab_faces(F, N, B=1):
     return int(_lib.load().vt_closest_point_mesh_slab_faces(int(F), int(N), int(B)))
 
 
-def closest_point_mesh(verts, faces, pts, want_point=True):
-    """ClosestPoint(d2 [N] f64, face [N] i32, closest [N,3] f64 or None) of the query points pts [N,3] f32 against the mesh (verts [V,3]
-    f32, faces [F,3] i32 / i64) on the device (vt_closest_point_mesh): the smallest squared distance to a closed triangle in float64, the
-    face that attains it (the lowest index among equals) and the point on it -- trimesh.proximity.closest_point (training.py:415).  A mesh
-    without vertices or faces, or a face index outside [0, V), raises VtError."""
-    what = "closest_point_mesh"
+def _cp_tensors(what, verts, faces, pts):
+    """The three arguments of a closest-point call, checked and contiguous (faces as int32)."""
     if not (torch.is_tensor(verts) and torch.is_tensor(faces) and torch.is_tensor(pts)):
         raise VtError(f"{what}: verts, faces and pts must be tensors")
     if not (verts.is_cuda and faces.is_cuda and pts.is_cuda) or verts.device != faces.device or verts.device != pts.device:
@@ -111,7 +108,22 @@ def closest_point_mesh(verts, faces, pts, want_point=True):
         raise VtError(f"{what}: expected verts [V,3], faces [F,3] and pts [N,3] (got {tuple(verts.shape)}, {tuple(faces.shape)}, {tuple(pts.shape)})")
     if verts.dtype != torch.float32 or pts.dtype != torch.float32 or faces.dtype not in (torch.int32, torch.int64):
         raise VtError(f"{what}: verts and pts must be float32 and faces int32 or int64 (got {verts.dtype}, {pts.dtype}, {faces.dtype})")
-    verts, faces, pts = _c(verts), _c(faces.to(I32)), _c(pts)
+    return _c(verts), _c(faces.to(I32)), _c(pts)
+
+
+def closest_point_mesh(verts, faces, pts, want_point=True, method='brute'):
+    """ClosestPoint(d2 [N] f64, face [N] i32, closest [N,3] f64 or None) of the query points pts [N,3] f32 against the mesh (verts [V,3]
+    f32, faces [F,3] i32 / i64) on the device (vt_closest_point_mesh): the smallest squared distance to a closed triangle in float64, the
+    face that attains it (the lowest index among equals) and the point on it -- trimesh.proximity.closest_point (training.py:415).  A mesh
+    without vertices or faces, or a face index outside [0, V), raises VtError.  ``method='tree'`` builds the face octree and walks it
+    (``closest_point_tree_build``, ``closest_point_tree_query``): the same bits from far fewer faces per query on a large mesh."""
+    what = "closest_point_mesh"
+    if method == 'tree':
+        _cp_tensors(what, verts, faces, pts)
+        return closest_point_tree_query(closest_point_tree_build(verts, faces), pts, want_point=want_point)
+    if method != 'brute':
+        raise VtError(f"{what}: method must be 'brute' or 'tree' (got {method!r})")
+    verts, faces, pts = _cp_tensors(what, verts, faces, pts)
     V, F, N = verts.shape[0], faces.shape[0], pts.shape[0]
     dev = pts.device
     d2 = torch.empty((N,), dtype=torch.float64, device=dev)
@@ -163,3 +175,100 @@ def closest_point_mesh_scenes(meshes, pts, want_point=True):
                                            ctypes.c_void_p(ws.data_ptr()), ws.numel() * 4, stream_ptr()), "vt_closest_point_mesh_scenes")
     _cp_status(ws, what)
     return ClosestPoint(d2, face, closest)
+
+
+class ClosestTree:
+    """The face octree of a mesh with what a closest-point walk reads (vt_closest_tree_build): ``tree`` (the ``ops.winding.Tree``, shared
+    with the fast winding number), ``side`` (the device buffer of boxes and face records), ``status`` (the build's status word: bit 0,
+    a face index outside [0, V)).  The views below alias ``side``."""
+
+    def __init__(self, tree, side, offsets, status):
+        self.tree, self.side, self._offsets, self.status = tree, side, offsets, int(status)
+
+    def boxes(self, level):
+        """float64 [counts[level], 6]: lo[3], hi[3] of the level's occupied cells, in the order of the tree's records."""
+        base, n = sum(self.tree.counts[:level]), self.tree.counts[level]
+        at = self._offsets[0] + 48 * base
+        return self.side.view(torch.uint8)[at:at + 48 * n].view(torch.float64).view(-1, 6)
+
+    @property
+    def records(self):
+        """float64 [F, 14]: the face records in list order (slot t is face ``tree.lists[t]``)."""
+        at = self._offsets[1]
+        return self.side.view(torch.uint8)[at:at + 112 * self.tree.n_faces].view(torch.float64).view(-1, 14)
+
+
+def closest_point_tree_build(verts, faces, depth=None, tree=None):
+    """The ClosestTree of the mesh (verts [V,3] f32, faces [F,3] i32 / i64 on the device): ``ops.winding.build``'s octree (``depth`` as
+    there), or the caller's ``tree`` of the same mesh -- sign and distance then share one build -- with one bounding box per occupied
+    cell and the faces' records in list order.  One host read (the status word) at the end.  A mesh without vertices or faces raises
+    VtError, as ``closest_point_mesh`` does; a face index outside [0, V) is kept in ``status`` and raised by the query."""
+    from . import winding
+    what = "closest_point_tree_build"
+    if not (torch.is_tensor(verts) and torch.is_tensor(faces)) or not (verts.is_cuda and faces.is_cuda) or verts.device != faces.device:
+        raise VtError(f"{what}: verts and faces must be tensors on one HIP device; vtaco_amd has no CPU path")
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise VtError(f"{what}: expected verts [V,3] and faces [F,3] (got {tuple(verts.shape)} and {tuple(faces.shape)})")
+    if verts.dtype != torch.float32 or faces.dtype not in (torch.int32, torch.int64):
+        raise VtError(f"{what}: verts must be float32 and faces int32 or int64 (got {verts.dtype}, {faces.dtype})")
+    verts, faces = _c(verts), _c(faces.to(I32))
+    V, F = verts.shape[0], faces.shape[0]
+    if V == 0 or F == 0:
+        raise VtError(f"{what}: a mesh without vertices or faces has no closest point")
+    if tree is None:
+        tree = winding.build(verts, faces, depth)
+    elif tree.n_faces != F or tree.device != verts.device or (depth is not None and int(depth) != tree.depth):
+        raise VtError(f"{what}: the tree given is not one of this mesh ({tree.n_faces} faces at depth {tree.depth} on {tree.device})")
+    lib = _lib.load()
+    offsets = (ctypes.c_size_t * 3)()
+    check(lib.vt_closest_tree_layout(F, tree.depth, tree._state, offsets), "vt_closest_tree_layout")
+    side = torch.empty((offsets[2] + 7) // 8, dtype=torch.int64, device=verts.device)
+    check(lib.vt_closest_tree_build(dev_ptr(verts, "verts"), V, dev_ptr(faces, "faces", I32), F, tree.depth, tree._state,
+                                    ctypes.c_void_p(tree.buf.data_ptr()), tree.buf.numel() * 8, ctypes.c_void_p(side.data_ptr()), side.numel() * 8,
+                                    stream_ptr()), "vt_closest_tree_build")
+    return ClosestTree(tree, side, list(offsets), side[:1].view(I32)[0].item())
+
+
+def closest_point_tree_query(ctree, pts, want_point=True, stats=False, strict=True):
+    """``closest_point_mesh``'s ClosestPoint of pts [N,3] f32 against a ClosestTree, bit for bit (vt_closest_tree_query: a walk of the octree
+    that skips every cell whose box is farther than the best face so far; reads nothing back).  With ``stats`` also int32 [N,2]: the boxes
+    and the faces tested per query.  A tree whose mesh has a face index outside [0, V) raises VtError as the brute-force call does;
+    ``strict=False`` answers from the other faces instead."""
+    what = "closest_point_tree_query"
+    if not isinstance(ctree, ClosestTree):
+        raise VtError(f"{what}: expected a ClosestTree (closest_point_tree_build)")
+    if not torch.is_tensor(pts) or pts.dim() != 2 or pts.shape[1] != 3 or pts.dtype != torch.float32 or pts.device != ctree.tree.device:
+        raise VtError(f"{what}: pts must be a float32 [N,3] tensor on the tree's device")
+    if strict and ctree.status & 1:
+        raise VtError(f"{what}: a face index lies outside [0, V) (found on the device by the build; that face was not read)")
+    pts = _c(pts)
+    N, dev, t = pts.shape[0], pts.device, ctree.tree
+    d2 = torch.empty((N,), dtype=torch.float64, device=dev)
+    face = torch.empty((N,), dtype=I32, device=dev)
+    closest = torch.empty((N, 3), dtype=torch.float64, device=dev) if want_point else None
+    st = torch.empty((N, 2), dtype=I32, device=dev) if stats else None
+    check(_lib.load().vt_closest_tree_query(ctypes.c_void_p(t.buf.data_ptr()), t.buf.numel() * 8, ctypes.c_void_p(ctree.side.data_ptr()),
+                                            ctree.side.numel() * 8, t.n_faces, t.depth, t._state, dev_ptr(pts, "pts") if N else None, N,
+                                            dev_ptr(d2, "d2", torch.float64) if N else None, dev_ptr(face, "face", I32) if N else None,
+                                            dev_ptr(closest, "closest", torch.float64) if want_point and N else None,
+                                            dev_ptr(st, "stats", I32) if stats and N else None, stream_ptr()), "vt_closest_tree_query")
+    out = ClosestPoint(d2, face, closest)
+    return (out, st) if stats else out
+
+
+def closest_point_tree_query_scenes(ctrees, pts, want_point=True, stats=False, strict=True):
+    """pts [B,N,3] against one ClosestTree per scene -> ClosestPoint(d2 [B,N], face [B,N], closest [B,N,3]) (and stats [B,N,2]): one launch
+    per scene, each equal to its single call."""
+    what = "closest_point_tree_query_scenes"
+    if not torch.is_tensor(pts) or pts.dim() != 3 or pts.shape[2] != 3 or len(ctrees) != pts.shape[0]:
+        raise VtError(f"{what}: {len(ctrees)} trees for points {tuple(pts.shape) if torch.is_tensor(pts) else pts}")
+    res = [closest_point_tree_query(t, pts[b], want_point=want_point, stats=stats, strict=strict) for b, t in enumerate(ctrees)]
+    cps = [r[0] for r in res] if stats else res
+    B, N = pts.shape[:2]
+    if B == 0:
+        empty = ClosestPoint(torch.empty((0, N), dtype=torch.float64, device=pts.device), torch.empty((0, N), dtype=I32, device=pts.device),
+                             torch.empty((0, N, 3), dtype=torch.float64, device=pts.device) if want_point else None)
+        return (empty, torch.empty((0, N, 2), dtype=I32, device=pts.device)) if stats else empty
+    out = ClosestPoint(torch.stack([c.d2 for c in cps]), torch.stack([c.face for c in cps]),
+                       torch.stack([c.closest for c in cps]) if want_point else None)
+    return (out, torch.stack([r[1] for r in res])) if stats else out

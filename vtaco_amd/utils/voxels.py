@@ -116,6 +116,27 @@ def voxelize_fill(mesh, resolution):
     return _fill(*_mesh_tensors(mesh), resolution, *_UNIT)
 
 
+def signed_distance_field(mesh, resolution, loc=None, scale=None, winding='fast', distance='tree'):
+    """float64 [resolution]^3 on the device: ``eval.signed_distance`` of the mesh at the voxel centres of ``VoxelGrid``'s lattice, in its
+    [x][y][z] order -- the distance to the surface, negative inside.  ``loc`` / ``scale`` as ``VoxelGrid.from_mesh`` takes them (by
+    default the bounds' centre and the scale that puts the mesh into [-0.45, 0.45]^3 of the grid).  The defaults take sign and distance
+    from one octree (``ops.winding``, ``ops.metrics.closest_point_tree_query``: the exact closest point); ``winding='exact'`` and
+    ``distance='brute'`` test every face per voxel."""
+    from ..eval import signed_distance
+    v, f = _mesh_tensors(mesh)
+    if v.shape[0] == 0 or f.shape[0] == 0:
+        raise ValueError("signed_distance_field: a mesh without vertices or faces has no distance field")
+    if loc is None or scale is None:
+        lo, hi = v.double().min(0).values.cpu().numpy(), v.double().max(0).values.cpu().numpy()
+        if loc is None:
+            loc = (lo + hi) / 2
+        if scale is None:
+            scale = (hi - lo).max() / 0.9
+    res = int(resolution)
+    pts = _centres(res, np.asarray(loc, dtype=np.float64), float(scale), v.device).reshape(-1, 3)
+    return signed_distance(pts, v, f, winding=winding, distance=distance).reshape(res, res, res)
+
+
 class VoxelGrid:
     def __init__(self, data, loc=(0., 0., 0.), scale=1):
         if len(data.shape) != 3 or not (data.shape[0] == data.shape[1] == data.shape[2]):
