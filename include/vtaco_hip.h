@@ -1637,6 +1637,41 @@ int vt_closest_tree_build(const float *verts, int64_t V, const int32_t *faces, i
 int vt_closest_tree_query(const void *tree, size_t tree_bytes, const void *side, size_t side_bytes, int64_t F, int depth, const int32_t *state_host,
                           const float *pts, int64_t N, double *d2, int32_t *face, double *closest, int32_t *stats, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------ */
+/* What a ray hits first on a mesh, and the sensor camera on it (csrc/ray_mesh.hip; DESIGN.md section "ray_mesh.hip";                     */
+/* tests/ray_mesh_ref.py restates it in numpy).  Stands where a trimesh.Trimesh offers mesh.ray.intersects_first /                        */
+/* intersects_location; the reference takes its tactile depth images from a simulator outside its tree.                                  */
+/* Rays are o + s d in float64, d NOT normalised, s in units of d: origins [N / rays_per_origin][3] (ray n starts at origin               */
+/* n / rays_per_origin: 1 for one origin per ray, N for one origin, H * W for camera images), dirs [N][3].  The rule is the watertight   */
+/* test of Woop, Benthin and Wald (2013), two-sided, in float64 (csrc/ray_face.h): zeros are accepted on both sides of an edge and the   */
+/* two faces of an edge compute exact negatives there, so no ray passes between them.  Per ray: s [N] f64 the smallest hit parameter in  */
+/* [t_min, t_max], face [N] i32 its face (the lowest index among equal s), bary NULL or [N][3] f64 the weights of the face's three        */
+/* corners.  A miss is +inf, -1, NaN weights.  A ray with a zero direction, or an origin or direction that is not finite, misses.         */
+/*   vt_ray_mesh         every face per ray: the definition.  workspace: vt_ray_mesh_workspace_bytes(F, N) bytes (0 for F <= 0); its     */
+/*                       first int32 is the status word (bit 0: a face index outside [0, V); that face is never read).                  */
+/*   vt_ray_tree_query   the same s, face and weights, bit for bit, from a walk of a built winding tree and its closest-point side       */
+/*                       buffer (vt_winding_tree_build, vt_closest_tree_build: nothing more is built per mesh; the side buffer's status   */
+/*                       word reports a bad index).  A cell is skipped when the segment [t_min, min(t_max, best)] misses its box grown    */
+/*                       by 2^-40 S (S from the frame and the origin).  stats NULL or [N][2] int32 (boxes tested, faces tested).          */
+/*                       VTACO_RAY_TREE_WALK = plain | order (the default) picks the walk: equal results.                                 */
+/*   vt_camera_rays      the inverse of vt_contact_points' unprojection, from the same pose records [n_images][16] f64: origins           */
+/*                       [n_images][3] = (t - centroid) / scale, dirs [n_images][height * width][3] = M (1, -(u - W/2) / f,               */
+/*                       -(v - H/2) / f) / scale, f = height / (2 tan(fov / 2)).  The camera-axis component is 1, so the s of a hit is    */
+/*                       the planar depth vt_contact_points and vt_depth_cloud unproject.                                                 */
+/*   vt_depth_from_hits  depth [N] f32 = min(s, depth_origin[n % n_pixels]) clamped below at `near`; depth_origin NULL: no minimum (a     */
+/*                       miss stays +inf).                                                                                                */
+/* All four are asynchronous, read nothing back and allocate nothing.  Errors, all before any launch: a NULL array, a negative size, a   */
+/*   mesh without vertices or faces, or rays_per_origin < 1 is VT_ERR_INVALID; depth outside [1, VT_WN_MAX_DEPTH] VT_ERR_UNSUPPORTED;    */
+/*   a short workspace, tree or side buffer VT_ERR_WORKSPACE.  N == 0 launches nothing.                                                  */
+size_t vt_ray_mesh_workspace_bytes(int F, int64_t N);
+int vt_ray_mesh(const float *verts, int V, const int32_t *faces, int F, const double *origins, int64_t rays_per_origin, const double *dirs, int64_t N,
+                double t_min, double t_max, double *s, int32_t *face, double *bary, void *workspace, size_t workspace_bytes, void *stream);
+int vt_ray_tree_query(const void *tree, size_t tree_bytes, const void *side, size_t side_bytes, int64_t F, int depth, const int32_t *state_host,
+                      const double *origins, int64_t rays_per_origin, const double *dirs, int64_t N, double t_min, double t_max, double *s,
+                      int32_t *face, double *bary, int32_t *stats, void *stream);
+int vt_camera_rays(const double *pose, int n_images, int width, int height, double fov_deg, double *origins, double *dirs, void *stream);
+int vt_depth_from_hits(const double *s, const double *depth_origin, int64_t n_pixels, int64_t N, double near, float *depth, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

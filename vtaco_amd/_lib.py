@@ -424,6 +424,11 @@ SIGNATURES = {
     "vt_closest_tree_layout": (_I, [_I64, _I, _VP, _VP]),
     "vt_closest_tree_build": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _VP, _SZ, _VP, _SZ, _VP]),
     "vt_closest_tree_query": (_I, [_VP, _SZ, _VP, _SZ, _I64, _I, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP]),   # trimesh.proximity.closest_point
+    "vt_ray_mesh_workspace_bytes": (_SZ, [_I, _I64]),
+    "vt_ray_mesh": (_I, [_VP, _I, _VP, _I, _VP, _I64, _VP, _I64, _D, _D, _VP, _VP, _VP, _VP, _SZ, _VP]),   # trimesh ray.intersects_first
+    "vt_ray_tree_query": (_I, [_VP, _SZ, _VP, _SZ, _I64, _I, _VP, _VP, _I64, _VP, _I64, _D, _D, _VP, _VP, _VP, _VP, _VP]),
+    "vt_camera_rays": (_I, [_VP, _I, _I, _I, _D, _VP, _VP, _VP]),
+    "vt_depth_from_hits": (_I, [_VP, _VP, _I64, _I64, _D, _VP, _VP]),
 }
 
 _lib = None

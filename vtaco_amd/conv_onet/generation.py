@@ -107,6 +107,23 @@ class Mesh(namedtuple("Mesh", ["vertices", "faces"])):
         from ..utils import voxels
         return voxels.signed_distance_field(self, resolution, loc=loc, scale=scale, winding=winding, distance=distance)
 
+    def ray_cast(self, origins, dirs, t_min=0.0, t_max=float("inf"), method=None, tree=None, bary=False):
+        """(s f64 [N], face i32 [N][, bary f64 [N,3]]): what the rays ``origins + s dirs`` hit first (``ops.rays.ray_mesh``)."""
+        from ..utils.voxels import _mesh_tensors
+        v, f = _mesh_tensors(self)
+        return ops.rays.ray_mesh(v, f, origins, dirs, t_min=t_min, t_max=t_max, method=method, tree=tree, bary=bary)
+
+    def render_depth(self, cam_pos, cam_rot, height=240, width=320, fov=60.0, pc_ply=None, centroid=None, scale=None, method='tree'):
+        """(depth f32 [n,H,W], face i32 [n,H,W]): this mesh seen from n sensor poses (utils/render.py)."""
+        from ..utils import render
+        return render.render_depth(self, cam_pos, cam_rot, height=height, width=width, fov=fov, pc_ply=pc_ply, centroid=centroid, scale=scale,
+                                   method=method)
+
+    def simulate_touch(self, cam_pos, cam_rot, depth_origin, near=0.019, threshold=1e-4, **kw):
+        """(depth f32 [n, H*W], touch_success bool [n]): the depth images of n sensors pressed against this mesh (utils/render.py)."""
+        from ..utils import render
+        return render.simulate_touch(self, cam_pos, cam_rot, depth_origin, near=near, threshold=threshold, **kw)
+
 
 _tensor_version = operator.attrgetter("_version")
 
