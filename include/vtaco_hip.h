@@ -1638,6 +1638,60 @@ int vt_closest_tree_query(const void *tree, size_t tree_bytes, const void *side,
                           const float *pts, int64_t N, double *d2, int32_t *face, double *closest, int32_t *stats, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------------------------ */
+/* Nearest point of a point set through an octree over the points (csrc/point_tree.hip; DESIGN.md section "point_tree.hip";               */
+/* tests/point_tree_ref.py restates it in numpy): vt_nn_points' d2 and idx, bit for bit, without testing every target.  Stands where the   */
+/* reference searches a kd-tree (src/utils/icp.py:50-66, src/common.py:94-175).  B problems per call, dst [B][M][3] f64 with one M and    */
+/* one depth; every kernel covers the batch in one launch.  Frame, cells, Morton numbering, pyramids and lists are the winding tree's      */
+/* with points for centroids; each occupied cell carries the tight box lo[3], hi[3] of its points; the points are copied in list order.    */
+/*   vt_point_tree_default_depth  the smallest L in 1 .. VT_WN_MAX_DEPTH with 8^L * 8 >= M                                                 */
+/*   vt_point_tree_count    frames, leaf codes, the pyramids and the list offsets of all B problems, into the workspace                    */
+/*                          (vt_point_tree_workspace_bytes(M, B, depth) bytes, 0 for sizes outside the limits).  Its first 16 B int32      */
+/*                          are the state words the caller reads back, once per batch: per problem word 0 the status (bit 0: a target      */
+/*                          coordinate is not finite), words 1 .. 1 + depth the occupied cells of level 0 .. depth.                        */
+/*   vt_point_tree_layout   host only: from those words, offsets[0..4] = the byte offsets inside one problem's tree of the pyramids        */
+/*                          (int32, level l at word (8^l - 1) / 7), the boxes (6 f64 per cell), the list offsets (int32, leaves + 1), the  */
+/*                          lists (int32 [M]) and the points in list order (f64 [M][3]); offsets[5] = the bytes from one problem's tree     */
+/*                          to the next, offsets[6] = the bytes of all B.  The per-problem descriptors: every problem's tree has the same  */
+/*                          offsets, a level's boxes having room for that level's largest count over the batch (level l starts at box      */
+/*                          sum of those maxima over the levels above); the launch functions recompute this from state_host and pass it     */
+/*                          to the kernels by value, which find their problem at blockIdx.y * offsets[5].  Bytes past a problem's own      */
+/*                          counts are not written.                                                                                        */
+/*   vt_point_tree_build    lists, points, boxes and headers into `tree`; the same workspace, untouched since the count.  A status word     */
+/*                          != 0 is VT_ERR_INVALID ("a target coordinate is not finite").                                                  */
+/*   vt_point_tree_query    (asynchronous, allocates nothing, reads nothing back, safe to capture) src [B][N][3] f64, T [B][4][4] or NULL   */
+/*                          (applied to src first, vt_nn_points' arithmetic) -> d2 [B][N] f64, idx [B][N] i32; stats NULL or [B][N][2]     */
+/*                          int32: boxes tested, points tested.  One lane per query, a walk without a stack that skips a cell exactly      */
+/*                          when its box's lower bound exceeds the best d2 so far.  VTACO_POINT_TREE_WALK = plain | seed | order |         */
+/*                          seed+order (the default) picks the walk; all give equal results.                                               */
+/*                          perm NULL or [B][N] i32, a permutation of 0 .. N-1 per problem: lane i answers query perm[i].  Outputs stay    */
+/*                          in query order; no result depends on it.                                                                      */
+/*   vt_point_tree_lanes    perm for vt_point_tree_query: the queries (moved by T when given) in Morton order of the tree's leaves, by      */
+/*                          count / scan / fill through an integer cursor; the order inside a leaf is whatever the cursor hands out.       */
+/*                          workspace: vt_point_tree_lanes_workspace_bytes(N, B, depth).  Asynchronous, reads nothing back.                */
+/* Errors, all before any launch: a NULL array, M < 1, N < 1 or B outside [1, 65535] is VT_ERR_INVALID, as are counts no tree of this size  */
+/* has; depth outside [1, VT_WN_MAX_DEPTH] is VT_ERR_UNSUPPORTED; a short workspace or tree VT_ERR_WORKSPACE.                              */
+/* vt_icp_tree -- vt_icp with the neighbour search of every iteration done by vt_point_tree_query on the built trees of Bp (tree, depth,    */
+/*   state_host as above); the partners are still read from Bp through idx.  Fit, move, state and the gate of finished problems are        */
+/*   vt_icp's: equal bits in every output.  Enqueued in full, no host read.  morton_lanes != 0: the queries are handed to lanes in the    */
+/*   order vt_point_tree_lanes gives for the working copy the loop starts with, built once.  workspace:                                  */
+/*   vt_icp_tree_workspace_bytes(N, B, depth).                                                                                           */
+int vt_point_tree_default_depth(int64_t M);
+size_t vt_point_tree_workspace_bytes(int64_t M, int B, int depth);
+int vt_point_tree_count(const double *dst, int64_t M, int B, int depth, void *workspace, size_t workspace_bytes, void *stream);
+int vt_point_tree_layout(int64_t M, int depth, int B, const int32_t *state_host, size_t *offsets);
+int vt_point_tree_build(const double *dst, int64_t M, int B, int depth, const int32_t *state_host, void *workspace, size_t workspace_bytes, void *tree,
+                        size_t tree_bytes, void *stream);
+int vt_point_tree_query(const void *tree, size_t tree_bytes, int64_t M, int depth, int B, const int32_t *state_host, const double *src, int64_t N,
+                        const double *T, double *d2, int32_t *idx, int32_t *stats, const int32_t *perm, void *stream);
+size_t vt_point_tree_lanes_workspace_bytes(int64_t N, int B, int depth);
+int vt_point_tree_lanes(const void *tree, size_t tree_bytes, int64_t M, int depth, int B, const int32_t *state_host, const double *src, int64_t N,
+                        const double *T, int32_t *perm, void *workspace, size_t workspace_bytes, void *stream);
+size_t vt_icp_tree_workspace_bytes(int64_t N, int B, int depth);
+int vt_icp_tree(const double *A, int64_t N, const double *Bp, int64_t M, int B, const void *tree, size_t tree_bytes, int depth,
+                const int32_t *state_host, int morton_lanes, const double *init_pose, int max_iterations, double tolerance, double *T,
+                double *distances, int32_t *idx, int32_t *iterations, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------------------------ */
 /* What a ray hits first on a mesh, and the sensor camera on it (csrc/ray_mesh.hip; DESIGN.md section "ray_mesh.hip";                     */
 /* tests/ray_mesh_ref.py restates it in numpy).  Stands where a trimesh.Trimesh offers mesh.ray.intersects_first /                        */
 /* intersects_location; the reference takes its tactile depth images from a simulator outside its tree.                                  */

@@ -397,6 +397,16 @@ SIGNATURES = {
     "vt_icp_fit": (_I, [_VP, _VP, _I64, _I64, _VP, _I, _VP, _VP, _SZ, _VP]),                         # best_fit_transform, utils/icp.py:5-47
     "vt_icp_workspace_bytes": (_SZ, [_I64, _I64, _I]),
     "vt_icp": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _I, _D, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),       # icp, utils/icp.py:69-121
+    "vt_point_tree_default_depth": (_I, [_I64]),
+    "vt_point_tree_workspace_bytes": (_SZ, [_I64, _I, _I]),
+    "vt_point_tree_count": (_I, [_VP, _I64, _I, _I, _VP, _SZ, _VP]),
+    "vt_point_tree_layout": (_I, [_I64, _I, _I, _VP, _VP]),
+    "vt_point_tree_build": (_I, [_VP, _I64, _I, _I, _VP, _VP, _SZ, _VP, _SZ, _VP]),
+    "vt_point_tree_query": (_I, [_VP, _SZ, _I64, _I, _I, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP]),  # the kd-tree queries of icp.py:50-66, common.py:142-175
+    "vt_point_tree_lanes_workspace_bytes": (_SZ, [_I64, _I, _I]),
+    "vt_point_tree_lanes": (_I, [_VP, _SZ, _I64, _I, _I, _VP, _VP, _I64, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_icp_tree_workspace_bytes": (_SZ, [_I64, _I, _I]),
+    "vt_icp_tree": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _SZ, _I, _VP, _I, _VP, _I, _D, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "vt_mesh_components_workspace_bytes": (_SZ, [_I64, _I64]),
     "vt_mesh_components": (_I, [_VP, _I64, _I64, _VP, _IP, _VP, _SZ, _VP]),                           # trimesh graph.connected_components
     "vt_mesh_component_table_workspace_bytes": (_SZ, [_I64, _I64]),

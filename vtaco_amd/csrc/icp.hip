@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "icp_common.h"
 #include "vt_common.h"
 #include "vtaco_hip.h"
 
@@ -55,16 +56,6 @@ NnPlan nn_plan(int64_t N, int64_t M, int B) {
     p.pidx_off = up256((size_t)N * p.slabs * sizeof(double));
     p.block_bytes = p.pidx_off + up256((size_t)N * p.slabs * sizeof(int32_t));
     return p;
-}
-
-// the loop's per-problem state; a NULL `done` never freezes
-struct Gate { const int32_t *done; const int32_t *iter; int it; };
-__device__ inline bool frozen(const Gate &g, int b) { return g.done && g.done[b] != 0 && g.iter[b] < g.it; }
-
-__device__ inline void move_point(const double *T, double x, double y, double z, double &ox, double &oy, double &oz) {
-    ox = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
-    oy = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
-    oz = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
 }
 
 // grid (query tiles, slabs, B): partial minimum of 256 queries over one slab of targets
@@ -353,11 +344,11 @@ void fit_launch(const double *a, const double *bp, const int32_t *idx, int N, in
                        prev_error, done, iter, it);
 }
 
-struct IcpPlan { NnPlan nn; size_t work_off, d2_off, t_off, prev_off, done_off, fit_off, nn_off, bytes; };
+// the loop's own buffers, then the neighbour search's (nn_bytes: 0 for the tree, which needs none)
+struct IcpPlan { size_t work_off, d2_off, t_off, prev_off, done_off, fit_off, nn_off, bytes; };
 
-IcpPlan icp_plan(int64_t N, int64_t M, int B) {
+IcpPlan icp_plan(int64_t N, int B, size_t nn_bytes) {
     IcpPlan p;
-    p.nn = nn_plan(N, M, B);
     p.work_off = 0;
     p.d2_off = p.work_off + up256((size_t)B * N * 3 * sizeof(double));
     p.t_off = p.d2_off + up256((size_t)B * N * sizeof(double));
@@ -365,8 +356,29 @@ IcpPlan icp_plan(int64_t N, int64_t M, int B) {
     p.done_off = p.prev_off + up256((size_t)B * sizeof(double));
     p.fit_off = p.done_off + up256((size_t)B * sizeof(int32_t));
     p.nn_off = p.fit_off + fit_bytes(N, B);
-    p.bytes = p.nn_off + (size_t)B * p.nn.block_bytes;
+    p.bytes = p.nn_off + nn_bytes;
     return p;
+}
+
+// icp.py:102-121 enqueued in full.  nn(work, d2, idx, gate) enqueues the neighbour search of one iteration and returns its error code;
+// fit, move, the state and the gate are the same whatever searches
+template <class Nn>
+int icp_loop(const double *A, int N, const double *Bp, int M, int B, const double *init_pose, int max_iterations, double tolerance, double *T,
+             double *distances, int32_t *idx, int32_t *iterations, char *ws, const IcpPlan &pl, hipStream_t st, Nn nn) {
+    double *work = reinterpret_cast<double *>(ws + pl.work_off), *d2 = reinterpret_cast<double *>(ws + pl.d2_off);
+    double *Tit = reinterpret_cast<double *>(ws + pl.t_off), *prev = reinterpret_cast<double *>(ws + pl.prev_off);
+    int32_t *done = reinterpret_cast<int32_t *>(ws + pl.done_off);
+    hipLaunchKernelGGL(icp_state_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, prev, done, iterations, B);
+    hipLaunchKernelGGL(move_points_kernel, dim3(tiles(N), (unsigned)B), dim3(ICP_THREADS), 0, st, A, init_pose, work, N, Gate{nullptr, nullptr, 0});
+    for (int it = 0; it < max_iterations; ++it) {
+        const Gate gate{done, iterations, it};
+        if (int rc = nn(work, d2, idx, gate)) return rc;
+        fit_launch(work, Bp, idx, N, M, B, d2, distances, Tit, ws + pl.fit_off, tolerance, prev, done, iterations, it, st);
+        hipLaunchKernelGGL(move_points_kernel, dim3(tiles(N), (unsigned)B), dim3(ICP_THREADS), 0, st, (const double *)work, (const double *)Tit, work, N,
+                           gate);
+    }
+    fit_launch(A, work, nullptr, N, N, B, nullptr, nullptr, T, ws + pl.fit_off, 0.0, nullptr, nullptr, nullptr, 0, st);
+    return 0;
 }
 
 }  // namespace
@@ -410,33 +422,60 @@ int vt_icp_fit(const double *a, const double *b, int64_t N, int64_t M, const int
 
 size_t vt_icp_workspace_bytes(int64_t N, int64_t M, int B) {
     if (!sizes_ok(N, M, B)) return 0;
-    return icp_plan(N, M, B).bytes;
+    return icp_plan(N, B, (size_t)B * nn_plan(N, M, B).block_bytes).bytes;
 }
 
 int vt_icp(const double *A, int64_t N, const double *Bp, int64_t M, int B, const double *init_pose, int max_iterations, double tolerance, double *T,
            double *distances, int32_t *idx, int32_t *iterations, void *workspace, size_t workspace_bytes, void *stream) {
     if (!sizes_ok(N, M, B) || !A || !Bp || !T || !distances || !idx || !iterations || max_iterations < 1 || !(tolerance >= 0.0))
         return vt_fail(VT_ERR_INVALID, "vt_icp: bad argument (N >= 1, M >= 1, 1 <= B <= 65535, max_iterations >= 1, tolerance >= 0)");
-    const IcpPlan pl = icp_plan(N, M, B);
-    if (pl.nn.slabs > 65535) return vt_fail(VT_ERR_UNSUPPORTED, "vt_icp");
+    const NnPlan nn = nn_plan(N, M, B);
+    const IcpPlan pl = icp_plan(N, B, (size_t)B * nn.block_bytes);
+    if (nn.slabs > 65535) return vt_fail(VT_ERR_UNSUPPORTED, "vt_icp");
     if (!workspace || workspace_bytes < pl.bytes) return vt_fail(VT_ERR_WORKSPACE, "vt_icp");
     char *ws = static_cast<char *>(workspace);
-    double *work = reinterpret_cast<double *>(ws + pl.work_off), *d2 = reinterpret_cast<double *>(ws + pl.d2_off);
-    double *Tit = reinterpret_cast<double *>(ws + pl.t_off), *prev = reinterpret_cast<double *>(ws + pl.prev_off);
-    int32_t *done = reinterpret_cast<int32_t *>(ws + pl.done_off);
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)N, m = (int)M;
-    hipLaunchKernelGGL(icp_state_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, prev, done, iterations, B);
-    hipLaunchKernelGGL(move_points_kernel, dim3(tiles(N), (unsigned)B), dim3(ICP_THREADS), 0, st, A, init_pose, work, n, Gate{nullptr, nullptr, 0});
-    for (int it = 0; it < max_iterations; ++it) {
-        const Gate gate{done, iterations, it};
-        nn_launch(work, nullptr, Bp, n, m, B, d2, idx, ws + pl.nn_off, pl.nn, gate, st);
-        fit_launch(work, Bp, idx, n, m, B, d2, distances, Tit, ws + pl.fit_off, tolerance, prev, done, iterations, it, st);
-        hipLaunchKernelGGL(move_points_kernel, dim3(tiles(N), (unsigned)B), dim3(ICP_THREADS), 0, st, (const double *)work, (const double *)Tit, work, n,
-                           gate);
-    }
-    fit_launch(A, work, nullptr, n, n, B, nullptr, nullptr, T, ws + pl.fit_off, 0.0, nullptr, nullptr, nullptr, 0, st);
+    if (int rc = icp_loop(A, n, Bp, m, B, init_pose, max_iterations, tolerance, T, distances, idx, iterations, ws, pl, st,
+                          [&](const double *work, double *d2, int32_t *ix, Gate gate) {
+                              nn_launch(work, nullptr, Bp, n, m, B, d2, ix, ws + pl.nn_off, nn, gate, st);
+                              return 0;
+                          }))
+        return rc;
     return vt_check(hipGetLastError(), "vt_icp");
+}
+
+// the tree loop's workspace: the loop's own buffers, then the lane permutation [B][N] and what building it needs
+size_t icp_tree_nn_bytes(int64_t N, int B, int depth) { return up256((size_t)B * N * sizeof(int32_t)) + pt_lanes_bytes(N, B, depth); }
+
+size_t vt_icp_tree_workspace_bytes(int64_t N, int B, int depth) {
+    if (!sizes_ok(N, 1, B) || depth < 1 || depth > VT_WN_MAX_DEPTH) return 0;
+    return icp_plan(N, B, icp_tree_nn_bytes(N, B, depth)).bytes;
+}
+
+int vt_icp_tree(const double *A, int64_t N, const double *Bp, int64_t M, int B, const void *tree, size_t tree_bytes, int depth,
+                const int32_t *state_host, int morton_lanes, const double *init_pose, int max_iterations, double tolerance, double *T,
+                double *distances, int32_t *idx, int32_t *iterations, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!sizes_ok(N, M, B) || !A || !Bp || !tree || !state_host || !T || !distances || !idx || !iterations || max_iterations < 1 || !(tolerance >= 0.0))
+        return vt_fail(VT_ERR_INVALID, "vt_icp_tree: bad argument (N >= 1, M >= 1, 1 <= B <= 65535, max_iterations >= 1, tolerance >= 0)");
+    PtQueryPlan plan;                             // the tree's own checks (depth, counts, size, the walk asked for) before anything is enqueued
+    if (int rc = pt_query_plan(tree_bytes, M, depth, B, state_host, N, &plan)) return rc;
+    const IcpPlan pl = icp_plan(N, B, icp_tree_nn_bytes(N, B, depth));
+    if (!workspace || workspace_bytes < pl.bytes) return vt_fail(VT_ERR_WORKSPACE, "vt_icp_tree");
+    char *ws = static_cast<char *>(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    int32_t *perm = morton_lanes ? reinterpret_cast<int32_t *>(ws + pl.nn_off) : nullptr;
+    char *lanes_ws = ws + pl.nn_off + up256((size_t)B * N * sizeof(int32_t));
+    if (int rc = icp_loop(A, (int)N, Bp, (int)M, B, init_pose, max_iterations, tolerance, T, distances, idx, iterations, ws, pl, st,
+                          [&](const double *work, double *d2, int32_t *ix, Gate gate) {
+                              // the lane order is taken once, from the working copy the loop starts with: a rigid motion keeps the
+                              // lanes of a wave neighbours of each other, which is all the order is for
+                              if (perm && gate.it == 0) pt_lanes_enqueue(plan, tree, work, nullptr, perm, lanes_ws, st);
+                              pt_query_enqueue(plan, tree, work, nullptr, d2, ix, nullptr, perm, gate.done, gate.iter, gate.it, st);
+                              return 0;
+                          }))
+        return rc;
+    return vt_check(hipGetLastError(), "vt_icp_tree");
 }
 
 }  // extern "C"

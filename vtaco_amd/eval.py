@@ -1,5 +1,6 @@
-"""Evaluation metrics of the reference (src/common.py:11-91, 142-154): the host functions as the reference writes them, the device
-forms of the two the visualise block calls (chamfer_distance_device, earth_mover_distance_device: HIP kernels), and the hand-object
+"""Evaluation metrics of the reference (src/common.py:11-175): the host functions as the reference writes them, the device
+forms of the two the visualise block calls (chamfer_distance_device, earth_mover_distance_device: HIP kernels), the kd-tree Chamfer
+distance on the point octree (chamfer_distance_kdtree, chamfer_distance), and the hand-object
 geometry of its eval_step (training.py:393-419) on vt_closest_point_mesh and vt_winding_number: signed_distance, penetration_depth,
 mesh_distances."""
 from __future__ import annotations
@@ -61,6 +62,35 @@ def chamfer_distance_device(points1, points2, give_id=False):
     if give_id:
         return chamfer, i_12.long(), i_21.long()
     return chamfer
+
+
+def chamfer_distance_kdtree(points1, points2, give_id=False):
+    """``chamfer_distance_kdtree`` (common.py:94-140) on the device: [B,T1,3] and [B,T2,3] HIP tensors of any two sizes, no truncation
+    rule -> chamfer1 + chamfer2 [B]: the mean over points1 of the squared distance to the nearest point of points2, plus the same the
+    other way.  Where the reference asks pykdtree, each side's octree answers (``ops.icp.point_tree_build`` / ``point_tree_query``:
+    float64, the lowest index among equal minima); the means are ``torch.mean`` over those float64 distances and the result is cast to
+    the inputs' dtype.  ``give_id``: the reference's tuple (chamfer1, chamfer2, idx_nn_12 [B,T1], idx_nn_21 [B,T2]), indices int64."""
+    from . import ops
+    from ._lib import VtError
+    if not (torch.is_tensor(points1) and torch.is_tensor(points2)) or points1.dim() != 3 or points2.dim() != 3:
+        raise VtError("chamfer_distance_kdtree: expected [B,T,3] point sets")
+    if points1.dtype != points2.dtype:
+        raise VtError(f"chamfer_distance_kdtree: point sets of two dtypes ({points1.dtype}, {points2.dtype})")
+    p1, p2 = points1.detach(), points2.detach()
+    d_12, i_12 = ops.icp.point_tree_query(ops.icp.point_tree_build(p2), p1)
+    d_21, i_21 = ops.icp.point_tree_query(ops.icp.point_tree_build(p1), p2)
+    chamfer1, chamfer2 = torch.mean(d_12, dim=1), torch.mean(d_21, dim=1)
+    if give_id:
+        return chamfer1.to(points1.dtype), chamfer2.to(points1.dtype), i_12.long(), i_21.long()
+    return (chamfer1 + chamfer2).to(points1.dtype)
+
+
+def chamfer_distance(points1, points2, use_kdtree=True, give_id=False):
+    """``chamfer_distance`` (common.py:54-66) on the device: ``chamfer_distance_kdtree`` by default, ``chamfer_distance_device`` (the
+    reference's naive form, its truncation rule included) with ``use_kdtree=False``; ``give_id`` goes to the tree form only, as there."""
+    if use_kdtree:
+        return chamfer_distance_kdtree(points1, points2, give_id=give_id)
+    return chamfer_distance_device(points1, points2)
 
 
 def earth_mover_distance_device(points1, points2, return_assignment=False):
@@ -222,20 +252,25 @@ def mesh_distances(pred_mesh, gt_mesh, n, generator=None, threshold=0.01, distan
     return {'accuracy': accuracy, 'completeness': completeness, 'chamfer_l1': 0.5 * (accuracy + completeness), 'f_score': f_score}
 
 
-def mesh_distances_aligned(pred_mesh, gt_mesh, n, generator=None, threshold=0.01, max_iterations=20, tolerance=1e-3, distance='brute'):
+def mesh_distances_aligned(pred_mesh, gt_mesh, n, generator=None, threshold=0.01, max_iterations=20, tolerance=1e-3, distance='brute',
+                           registration='brute'):
     """``mesh_distances`` after a rigid registration of the predicted mesh onto the ground truth, so that a pose offset of the prediction
     does not read as shape error.  Both surfaces are sampled exactly as ``mesh_distances`` samples them; ``ops.icp.icp`` maps the
     predicted samples onto the ground-truth samples (vt_icp, float64); its T moves the predicted vertices, per component
     ((T00 x + T01 y) + T02 z) + T03 in float64, rounded to float32.  Returns ``mesh_distances`` of the moved mesh against the ground truth
     from the same random draws (the generator is put back to where the sampling began, so it ends where one ``mesh_distances`` call
     leaves it), plus 'transform' (4x4 float64 numpy array) and 'icp_iterations' (int, the 0-based index of the last executed iteration).
-    ``distance`` is ``mesh_distances``'."""
+    ``distance`` is ``mesh_distances``'; ``registration='tree'`` searches the loop's neighbours in an octree over the ground-truth
+    samples (vt_icp_tree): the same transform, bit for bit."""
     from . import ops
+    from ._lib import VtError
+    if registration not in ('brute', 'tree'):
+        raise VtError(f"mesh_distances_aligned: registration must be 'brute' or 'tree' (got {registration!r})")
     (pv, pf), (gv, gf) = pred_mesh, gt_mesh
     state = generator.get_state() if generator is not None else torch.cuda.get_rng_state(pv.device)
     sp, _ = sample_mesh_surface(pv, pf, n, generator)
     sg, _ = sample_mesh_surface(gv, gf, n, generator)
-    fit = ops.icp.icp(sp, sg, max_iterations=max_iterations, tolerance=tolerance)
+    fit = ops.icp.icp(sp, sg, max_iterations=max_iterations, tolerance=tolerance, method=registration)
     T, v = fit.T, pv.double()
     moved = torch.stack([((T[r, 0] * v[:, 0] + T[r, 1] * v[:, 1]) + T[r, 2] * v[:, 2]) + T[r, 3] for r in range(3)], dim=1).float()
     if generator is not None:

@@ -4,6 +4,9 @@
     nearest_neighbor(src, dst) -> (distances, indices)                              icp.py:50-66
     icp(A, B, init_pose=None, max_iterations=20, tolerance=0.001) -> (T, distances, i)   icp.py:69-121
 
+``nearest_neighbor`` and ``icp`` take ``method='brute'`` (the default) or ``'tree'``: the octree of csrc/point_tree.hip where the reference
+has sklearn's kd-tree, with results equal to the brute force's bit for bit.
+
 numpy arrays in give float64 numpy arrays out (indices int64, ``i`` a Python int); they are moved to the current HIP device for the
 work.  Device tensors in give device tensors out (indices int32, ``i`` a 0-dim int32 tensor: nothing waits for the device).  Batches
 [B,N,3] give T [B,4,4], R [B,3,3], t [B,3], distances [B,N] and i [B].  There is no host path: without a HIP device every call raises.
@@ -54,25 +57,26 @@ def best_fit_transform(A, B):
     return T, R.contiguous(), t.contiguous()
 
 
-def nearest_neighbor(src, dst):
-    """(distances, indices): the Euclidean distance from every point of src to its nearest point of dst, and that point's index."""
+def nearest_neighbor(src, dst, method="brute"):
+    """(distances, indices): the Euclidean distance from every point of src to its nearest point of dst, and that point's index.
+    ``method='tree'`` searches an octree over dst (``ops.icp.point_tree_build``): the same bits."""
     (s, d), host = _device_points("nearest_neighbor", src, dst)
     from .. import ops
-    d2, idx = ops.icp.nn_points(s, d)
+    d2, idx = ops.icp.nn_points(s, d, method=method)
     dist = torch.sqrt(d2)
     if host:
         return dist.cpu().numpy(), idx.cpu().numpy().astype(np.int64)
     return dist, idx
 
 
-def icp(A, B, init_pose=None, max_iterations=20, tolerance=0.001):
+def icp(A, B, init_pose=None, max_iterations=20, tolerance=0.001, method="brute"):
     """Iterative closest point: (T, distances, i) -- the transform that maps A onto B, the last iteration's neighbour distances and the
-    0-based index of the last executed iteration."""
+    0-based index of the last executed iteration.  ``method='tree'`` searches an octree over B in every iteration: the same bits."""
     (a, b), host = _device_points("icp", A, B)
     if init_pose is not None and not torch.is_tensor(init_pose):
         init_pose = torch.from_numpy(np.ascontiguousarray(np.asarray(init_pose, dtype=np.float64))).to(a.device)
     from .. import ops
-    out = ops.icp.icp(a, b, init_pose=init_pose, max_iterations=max_iterations, tolerance=tolerance)
+    out = ops.icp.icp(a, b, init_pose=init_pose, max_iterations=max_iterations, tolerance=tolerance, method=method)
     if host:
         its = out.iterations.cpu().numpy()
         return out.T.cpu().numpy(), out.distances.cpu().numpy(), (int(its) if its.ndim == 0 else its.astype(np.int64))
