@@ -1110,6 +1110,60 @@ int vt_resnet_fwd(const float *x, int n_img, int H, int W, const vt_resnet_param
                   void *workspace, size_t workspace_bytes, float *out, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* Tactile feature encoder with Bottleneck blocks, eval mode                       */
+/*   (resnet2d_bneck.hip).  Replaces ResNet.forward with Bottleneck blocks          */
+/*   (src/layers.py:86-207: Resnet50 of the encoder registry, Resnet101 / 152):     */
+/*   per block conv1 1x1, conv2 3x3 (carries the stride), conv3 1x1 to 4 * width,   */
+/*   a 1x1 projection of the block input in the first block of EVERY stage          */
+/*   (layer1.0: 64 -> 256 at stride 1), Linear(2048, 100), Linear(100, classes).    */
+/*   x [n_img][3][H][W] (NCHW) -> out [n_img][num_classes].                         */
+/* vt_resnet_bneck_pack folds every BatchNorm into its conv (f64), fragment order;  */
+/*   a projecting block's conv3 and projection share ONE bias, b3 + b_proj summed   */
+/*   in f64.  Blob floats: the stem as [64][3][7][8] (kx padded to 8) + 64; per      */
+/*   block conv1.weight + width, conv2.weight + width, conv3.weight (+              */
+/*   downsample.0.weight) + 4 * width; linear.weight, then linear.bias, fc.weight   */
+/*   and fc.bias each padded to a multiple of 4 floats.                             */
+/* vt_resnet_bneck_fwd is 2 + 3 * (number of blocks) launches: the stem, conv1 (a   */
+/*   GEMM over pixels, bias, ReLU), conv2 (the 3x3 kernel of resnet2d.hip), conv3   */
+/*   with its skip (one GEMM over [conv2's output ; block input] in a projecting    */
+/*   block, the block input added in the epilogue otherwise), the tail.  Exact-f32  */
+/*   matrix core, fixed summation order that does not depend on n_img:              */
+/*   bit-reproducible, an image's features are the same bits in any batch.          */
+/* stage_out: NULL, or four device pointers (each may be NULL); a set pointer        */
+/*   receives the output of layer{s+1}, [n_img][Hs][Ws][4 * (64 << s)] channels-     */
+/*   last, by one extra copy launch (for verification).                             */
+/* Covered (vt_resnet_bneck_supported): what vt_resnet_supported covers, with the   */
+/*   tensors four times as wide: every buffer below 2^31 elements.  Workspace: four */
+/*   buffers of max over the stages s = 0..3 of n_img * Hs * Ws * 4 * (64 << s)      */
+/*   floats, Hs = ceil(H / 2^(s+2)), Ws alike.                                      */
+/* ------------------------------------------------------------------------- */
+typedef struct vt_resnet_bneck_block { /* layer{s}.{b}: conv1 [C][Cin][1][1], conv2 [C][C][3][3], conv3 [4C][C][1][1] */
+    const float *conv1_w;
+    vt_resnet_bn bn1;
+    const float *conv2_w;
+    vt_resnet_bn bn2;
+    const float *conv3_w;
+    vt_resnet_bn bn3;
+    const float *down_w;               /* downsample.0.weight [4C][Cin][1][1] (first block of layer1..4), else NULL */
+    vt_resnet_bn down_bn;              /* downsample.1 */
+} vt_resnet_bneck_block;
+typedef struct vt_resnet_bneck_params {
+    int32_t blocks_num[4];
+    int32_t num_classes;
+    const float *conv1_w;              /* conv1.weight [64][3][7][7] */
+    vt_resnet_bn bn1;
+    vt_resnet_bneck_block block[4][VT_RESNET_MAX_BLOCKS];
+    const float *linear_w, *linear_b;  /* linear [100][2048], [100] */
+    const float *fc_w, *fc_b;          /* fc [num_classes][100], [num_classes] */
+} vt_resnet_bneck_params;
+int vt_resnet_bneck_supported(const int32_t *blocks_num, int num_classes, int n_img, int H, int W);
+size_t vt_resnet_bneck_blob_bytes(const int32_t *blocks_num, int num_classes);
+size_t vt_resnet_bneck_workspace_bytes(const int32_t *blocks_num, int num_classes, int n_img, int H, int W);
+int vt_resnet_bneck_pack(const vt_resnet_bneck_params *params_host, float *blob, size_t blob_bytes, void *stream);
+int vt_resnet_bneck_fwd(const float *x, int n_img, int H, int W, const vt_resnet_bneck_params *dims_host, const float *blob,
+                        void *workspace, size_t workspace_bytes, float *out, float *const *stage_out, void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* Tactile feature encoder, train mode: forward with batch statistics and the      */
 /*   backward for every parameter (resnet2d_train.hip).  Replaces ResNet.forward   */
 /*   with BasicBlocks in train mode under autograd (src/layers.py:54-207) as        */

@@ -116,6 +116,19 @@ class ResnetParams(ctypes.Structure):
                 ("linear_w", ctypes.c_void_p), ("linear_b", ctypes.c_void_p), ("fc_w", ctypes.c_void_p), ("fc_b", ctypes.c_void_p)]
 
 
+class ResnetBneckBlock(ctypes.Structure):
+    """Mirror of ``vt_resnet_bneck_block``."""
+    _fields_ = [("conv1_w", ctypes.c_void_p), ("bn1", ResnetBn), ("conv2_w", ctypes.c_void_p), ("bn2", ResnetBn),
+                ("conv3_w", ctypes.c_void_p), ("bn3", ResnetBn), ("down_w", ctypes.c_void_p), ("down_bn", ResnetBn)]
+
+
+class ResnetBneckParams(ctypes.Structure):
+    """Mirror of ``vt_resnet_bneck_params``."""
+    _fields_ = [("blocks_num", ctypes.c_int32 * 4), ("num_classes", ctypes.c_int32), ("conv1_w", ctypes.c_void_p), ("bn1", ResnetBn),
+                ("block", (ResnetBneckBlock * VT_RESNET_MAX_BLOCKS) * 4),
+                ("linear_w", ctypes.c_void_p), ("linear_b", ctypes.c_void_p), ("fc_w", ctypes.c_void_p), ("fc_b", ctypes.c_void_p)]
+
+
 class ResnetBlockGrads(ctypes.Structure):
     """Mirror of ``vt_resnet_block_grads``."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("conv1_w", "bn1_w", "bn1_b", "conv2_w", "bn2_w", "bn2_b", "down_w", "down_bn_w", "down_bn_b")]
@@ -280,6 +293,11 @@ SIGNATURES = {
     "vt_resnet_workspace_bytes": (_SZ, [ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I]),
     "vt_resnet_pack": (_I, [ctypes.POINTER(ResnetParams), _VP, _SZ, _VP]),
     "vt_resnet_fwd": (_I, [_VP, _I, _I, _I, ctypes.POINTER(ResnetParams), _VP, _VP, _SZ, _VP, _VP]),
+    "vt_resnet_bneck_supported": (_I, [ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I]),
+    "vt_resnet_bneck_blob_bytes": (_SZ, [ctypes.POINTER(ctypes.c_int32), _I]),
+    "vt_resnet_bneck_workspace_bytes": (_SZ, [ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I]),
+    "vt_resnet_bneck_pack": (_I, [ctypes.POINTER(ResnetBneckParams), _VP, _SZ, _VP]),
+    "vt_resnet_bneck_fwd": (_I, [_VP, _I, _I, _I, ctypes.POINTER(ResnetBneckParams), _VP, _VP, _SZ, _VP, ctypes.POINTER(ctypes.c_void_p), _VP]),
     "vt_resnet_train_supported": (_I, [ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I, _I]),
     "vt_resnet_train_workspace_bytes": (_SZ, [ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I, _I]),
     "vt_resnet_train_fwd": (_I, [_VP, _I, _I, _I, _I, ctypes.POINTER(ResnetParams), _D, _VP, _SZ, _VP, _VP]),

@@ -24,7 +24,11 @@ from . import ops
 #                             csrc/unet2d_train.hip)
 #   VTACO_TACTILE_RESNET_TRAIN  the train-mode forward and backward of TactileResNet under autograd (vt_resnet_train_fwd / vt_resnet_bwd,
 #                             csrc/resnet2d_train.hip)
+#   VTACO_TACTILE_BOTTLENECK  the eval-mode forward of a Bottleneck TactileResNet (Resnet50 / 101 / 152: vt_resnet_bneck_fwd,
+#                             csrc/resnet2d_bneck.hip); VTACO_TACTILE_RESNET does not reach these nets.  Default "hip": the Resnet50
+#                             stage at five 320x240 images replays in 1.56 ms against the modules' 2.14 (profiles/resnet_bneck_bench.json)
 _TACTILE_UNET_DEFAULT = "hip"
+_TACTILE_BOTTLENECK_DEFAULT = "hip"
 _TACTILE_UNET_TRAIN_DEFAULT = "host"
 _TACTILE_RESNET_TRAIN_DEFAULT = "host"
 
@@ -38,6 +42,10 @@ def _kernel_mode(variable, default):
 
 def _tactile_resnet_mode():
     return _kernel_mode("VTACO_TACTILE_RESNET", "hip")
+
+
+def _tactile_bottleneck_mode():
+    return _kernel_mode("VTACO_TACTILE_BOTTLENECK", _TACTILE_BOTTLENECK_DEFAULT)
 
 
 def _tactile_unet_mode():
@@ -361,6 +369,33 @@ class _ResidualPair(nn.Module):
         return F.relu(y + skip)
 
 
+class _Bottleneck(nn.Module):
+    """1x1 reduce, 3x3 (carries the stride), 1x1 expand to 4 * channel, each with its BatchNorm, and an identity or 1x1-projected skip
+    (reference ``Bottleneck``, src/layers.py:86-126; parameter names conv1/bn1/conv2/bn2/conv3/bn3/downsample)."""
+    expansion = 4
+
+    def __init__(self, in_channel, out_channel, stride=1, downsample=None):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_channel, out_channel, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(out_channel)
+        self.conv2 = nn.Conv2d(out_channel, out_channel, 3, stride=stride, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(out_channel)
+        self.conv3 = nn.Conv2d(out_channel, out_channel * self.expansion, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(out_channel * self.expansion)
+        self.downsample = downsample
+
+    def forward(self, x, scenes=1):
+        if self.downsample is None:
+            skip = x
+        elif scenes > 1:
+            skip = _bn_scenes(self.downsample[1], self.downsample[0](x), scenes)
+        else:
+            skip = self.downsample(x)
+        y = F.relu(_bn_scenes(self.bn1, self.conv1(x), scenes))
+        y = F.relu(_bn_scenes(self.bn2, self.conv2(y), scenes))
+        return F.relu(_bn_scenes(self.bn3, self.conv3(y), scenes) + skip)
+
+
 class TactileResNet(nn.Module):
     """Tactile feature encoder of the shipped VTacO / VTacOH configs (``encoder_img: Resnet18``; reference ``ResNet`` with
     BasicBlocks, src/layers.py:127-195): 7x7/2 stem, 3x3/2 max-pool, four stages of residual pairs (64, 128, 256, 512; stride 2
@@ -369,10 +404,14 @@ class TactileResNet(nn.Module):
     (csrc/resnet2d.hip: BatchNorm folded into the convs, 18 launches for Resnet18, bit-reproducible).  In train mode under autograd
     with ``VTACO_TACTILE_RESNET_TRAIN=hip`` the forward and the backward are ``vt_resnet_train_fwd`` / ``vt_resnet_bwd``
     (csrc/resnet2d_train.hip: batch statistics per scene, every parameter's gradient, bit-reproducible; ``train_hip_supported``).
-    Everything else and ``VTACO_TACTILE_RESNET=host`` run the nn modules (``forward_modules``: host PyTorch-ROCm / MIOpen)."""
+    Everything else and ``VTACO_TACTILE_RESNET=host`` run the nn modules (``forward_modules``: host PyTorch-ROCm / MIOpen).
+    With ``block=_Bottleneck`` (Resnet50 / 101 / 152 of the reference: stages 256..2048 wide, Linear(2048, 100)) the eval forward is
+    ``vt_resnet_bneck_fwd`` (csrc/resnet2d_bneck.hip, 50 launches for Resnet50) under ``VTACO_TACTILE_BOTTLENECK=hip``; its train mode
+    runs the nn modules."""
 
-    def __init__(self, blocks_num=(2, 2, 2, 2), num_classes=32):
+    def __init__(self, blocks_num=(2, 2, 2, 2), num_classes=32, block=_ResidualPair):
         super().__init__()
+        self.block = block
         self.in_channel = 64
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -382,28 +421,34 @@ class TactileResNet(nn.Module):
         self.layer3 = self._stage(256, blocks_num[2], 2)
         self.layer4 = self._stage(512, blocks_num[3], 2)
         self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
-        self.linear = nn.Linear(512, 100)
+        self.linear = nn.Linear(512 * block.expansion, 100)
         self.fc = nn.Linear(100, num_classes)
         for m in self.modules():                                       # src/layers.py:150-152
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
 
     def _stage(self, channel, count, stride):
-        project = None
-        if stride != 1 or self.in_channel != channel:
-            project = nn.Sequential(nn.Conv2d(self.in_channel, channel, 1, stride=stride, bias=False), nn.BatchNorm2d(channel))
-        blocks = [_ResidualPair(self.in_channel, channel, stride=stride, downsample=project)]
-        self.in_channel = channel
-        blocks += [_ResidualPair(channel, channel) for _ in range(1, count)]
+        block, wide, project = self.block, channel * self.block.expansion, None
+        if stride != 1 or self.in_channel != wide:                     # src/layers.py:157-162 (a Bottleneck layer1.0 projects 64 -> 256)
+            project = nn.Sequential(nn.Conv2d(self.in_channel, wide, 1, stride=stride, bias=False), nn.BatchNorm2d(wide))
+        blocks = [block(self.in_channel, channel, stride=stride, downsample=project)]
+        self.in_channel = wide
+        blocks += [block(wide, channel) for _ in range(1, count)]
         return nn.Sequential(*blocks)
 
+    def _bottleneck(self):
+        return self.block is _Bottleneck
+
     def hip_supported(self, x):
-        """Eval mode, no autograd through the call, a HIP f32 image batch, a shape vt_resnet_supported covers."""
-        if self.training or _tactile_resnet_mode() != "hip" or not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
+        """Eval mode, no autograd through the call, a HIP f32 image batch, a shape vt_resnet_supported (vt_resnet_bneck_supported for a
+        Bottleneck net) covers."""
+        mode = _tactile_bottleneck_mode() if self._bottleneck() else _tactile_resnet_mode()
+        if self.training or mode != "hip" or not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
             return False
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             return False
-        return x.shape[1] == 3 and x.shape[0] > 0 and ops.resnet_supported(self, x.shape[0], x.shape[2], x.shape[3])
+        supported = ops.resnet_bneck.supported if self._bottleneck() else ops.resnet_supported
+        return x.shape[1] == 3 and x.shape[0] > 0 and supported(self, x.shape[0], x.shape[2], x.shape[3])
 
     def _blob_stamp(self):
         """(storage, version) of every parameter AND buffer: load_state_dict, an optimiser step and a train-mode forward (running
@@ -418,16 +463,16 @@ class TactileResNet(nn.Module):
         if hit is None or hit[0] != stamp:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("TactileResNet: weights changed since the last eager call; run one eval forward outside stream capture")
-            hit = (stamp, ops.resnet_pack(self))
+            hit = (stamp, (ops.resnet_bneck.pack if self._bottleneck() else ops.resnet_pack)(self))
             self.__dict__["_blob_cache"] = hit
         return hit[1]
 
     def _batchnorms(self):
-        """Every BatchNorm of the net: the stem's, each block's bn1 / bn2 and each projection's."""
+        """Every BatchNorm of the net: the stem's, each block's bn1 / bn2 (/ bn3) and each projection's."""
         bns = [self.bn1]
         for stage in (self.layer1, self.layer2, self.layer3, self.layer4):
             for blk in stage:
-                bns += [blk.bn1, blk.bn2] + ([blk.downsample[1]] if blk.downsample is not None else [])
+                bns += [blk.bn1, blk.bn2] + ([blk.bn3] if hasattr(blk, "bn3") else []) + ([blk.downsample[1]] if blk.downsample is not None else [])
         return bns
 
     def train_hip_supported(self, x, scenes=1):
@@ -455,7 +500,7 @@ class TactileResNet(nn.Module):
 
     def forward(self, x, scenes=1):
         if self.hip_supported(x):
-                return ops.resnet_fwd(x, self, self._blob())
+            return (ops.resnet_bneck.fwd if self._bottleneck() else ops.resnet_fwd)(x, self, self._blob())
         if self.train_hip_supported(x, scenes):
             return _TactileResNetTrain.apply(x, self, int(scenes), *[p for _, p in self.named_parameters()])
         return self.forward_modules(x, scenes)
@@ -484,3 +529,15 @@ def Resnet18(num_classes=32):
 
 def Resnet34(num_classes=32):
     return TactileResNet((3, 4, 6, 3), num_classes=num_classes)
+
+
+def Resnet50(num_classes=32):
+    return TactileResNet((3, 4, 6, 3), num_classes=num_classes, block=_Bottleneck)
+
+
+def Resnet101(num_classes=32):
+    return TactileResNet((3, 4, 23, 3), num_classes=num_classes, block=_Bottleneck)
+
+
+def Resnet152(num_classes=32):
+    return TactileResNet((3, 8, 36, 3), num_classes=num_classes, block=_Bottleneck)

@@ -6,7 +6,7 @@ tensors.  No function here computes anything with torch ops.
 
 This file only re-exports: callers write ``ops.name`` and look the name up at call time.  A switch that is assigned at run time
 (``decode_train.GRID_SCATTER_SORTED``, ``unet3d._WGRAD_UP``) is read by its own module: assign it there, not to the copy here.
-``resnet_train``, ``planes``, ``voxel_encoder``, ``points`` and ``voxelize`` are submodules only: callers write ``ops.resnet_train.fwd``,
+``resnet_train``, ``resnet_bneck``, ``planes``, ``voxel_encoder``, ``points`` and ``voxelize`` are submodules only: callers write ``ops.resnet_train.fwd``, ``ops.resnet_bneck.fwd``,
 ``ops.planes.sample_planes``, ``ops.voxel_encoder.encode_grid``, ``ops.points.point_sample``, ``ops.voxelize.surface``.
 ``ops.metrics`` is re-exported by the names of its ``__all__``; its closest-point launchers are reached as ``ops.metrics.closest_point_mesh``.
 ``icp`` is a submodule only as well: ``ops.icp.nn_points``, ``ops.icp.icp_fit``, ``ops.icp.icp``; so is ``mesh``: ``ops.mesh.components``,
@@ -15,7 +15,7 @@ This file only re-exports: callers write ``ops.name`` and look the name up at ca
 ``ops.winding.fast``, ``ops.winding.query_scenes`` (the exact sum stays ``ops.winding_number``), and so is ``rays``: ``ops.rays.ray_mesh``,
 ``ops.rays.ray_tree_query``, ``ops.rays.camera_rays``, ``ops.rays.depth_from_hits``.
 """
-from . import (_base, decode, decode_train, decode_wide, fusion, icp, labels, mano, mc, mesh, metrics, mise, nets2d, planes, pointnet, points, rays, resnet_train, touch,  # noqa: F401
+from . import (_base, decode, decode_train, decode_wide, fusion, icp, labels, mano, mc, mesh, metrics, mise, nets2d, planes, pointnet, points, rays, resnet_bneck, resnet_train, touch,  # noqa: F401
                unet3d, voxel, voxel_encoder, voxelize, winding)
 from ._base import *            # noqa: F401,F403
 from ._base import _c, _lib, _ptr_array     # noqa: F401
