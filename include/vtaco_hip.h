@@ -571,6 +571,14 @@ int vt_mc_echo_wait(int token, void *stream, int *nverts_host, int *nfaces_host,
 int vt_mc_emit(const float *vol, int n0, int n1, int n2, void *workspace,
                float *verts, int max_verts, int *faces, int max_faces,
                int rescale, float shift, float scale, void *stream);
+/* vt_mc_emit_normals: the other half of `vertices, faces, normals, values = measure.marching_cubes(value_grid,                    */
+/*   gradient_direction='ascent')` (src/conv_onet/generation.py:270; src/conv_onet/inferencing.py:174,316; Generator3D's            */
+/*   with_normals, generation.py:34,46): normals [nverts,3] f32, unit, array-axis order, and values [nverts] f32, rows in the       */
+/*   numbering of vt_mc_emit's vertices; rows beyond max_verts are dropped.  Runs behind vt_mc_count and vt_mc_emit on the same     */
+/*   vol and workspace (it reads the triangle lists, ranks and vertex bases they left there); asynchronous, one launch, no atomics, */
+/*   equal bits from run to run.  The rule is scikit-image 0.18.3's (tests/mc_normals_ref.py restates it): a normal that is zero    */
+/*   or not finite is (0,0,0).  A uniform rescale of the vertices leaves the normals as they are.                                   */
+int vt_mc_emit_normals(const float *vol, int n0, int n1, int n2, void *workspace, float *normals, float *values, int max_verts, void *stream);
 
 /* ------------------------------------------------------------------------- */
 /* Multiresolution isosurface extraction (MISE): one refinement step on the device.                                          */
@@ -1635,6 +1643,20 @@ size_t vt_mesh_cluster_place_workspace_bytes(int64_t K);
 int vt_mesh_cluster_place(const void *verts, int verts_f64, int64_t V, const int32_t *faces, int64_t F, int resolution, const int32_t *cluster_of_vertex,
                           const int32_t *cluster_rep, int64_t K, int placement, void *out_verts, int32_t *state, void *workspace, size_t workspace_bytes,
                           void *stream);
+
+/* ---- mesh normals (mesh_normals.hip) ----------------------------------------------------------------------------------------------- */
+/* Replaces: trimesh.Trimesh.face_normals / .vertex_normals of the meshes the reference builds (src/conv_onet/generation.py:273-284;     */
+/*   Generator3D's with_normals, generation.py:34,46).  tests/mesh_normals_ref.py restates the rule in numpy float64.                    */
+/* vt_mesh_normals: face_normals [F][3] and vertex_normals [V][3] in the vertices' type; either may be NULL, not both.  A face is        */
+/*   degenerate unless the squared length of (v1 - v0) x (v2 - v0), in float64, is positive and finite: its normal is (0,0,0) and it     */
+/*   adds nothing to a vertex.  weight 0 ('area'): a vertex sums the raw cross products of its faces; 1 ('angle'): their unit normals    */
+/*   times the interior angle at the vertex.  The sums are exact fixed-point accumulations by integer atomics (no float atomic), so      */
+/*   the result has equal bits from run to run and under any order of the faces; a vertex without a live face, or whose terms cancel     */
+/*   exactly, gets (0,0,0).  Sizes as in the topology block.  A face index outside [0, V) is never dereferenced and makes the call       */
+/*   VT_ERR_INVALID.  Waits for the stream (one read of the status word).                                                                */
+size_t vt_mesh_normals_workspace_bytes(int64_t V, int64_t F);
+int vt_mesh_normals(const void *verts, int verts_f64, int64_t V, const int32_t *faces, int64_t F, int weight, void *face_normals,
+                    void *vertex_normals, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------------------------ */
 /* Fast winding number (csrc/winding_fast.hip; DESIGN.md section "winding_fast.hip"; tests/winding_fast_ref.py restates it in numpy):     */

@@ -254,6 +254,7 @@ SIGNATURES = {
     "vt_mc_read_counts_begin": (_I, [_VP, _VP, ctypes.POINTER(_I)]),
     "vt_mc_read_counts_end": (_I, [_I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_D)]),
     "vt_mc_emit": (_I, [_VP, _I, _I, _I, _VP, _VP, _I, _VP, _I, _I, _F, _F, _VP]),
+    "vt_mc_emit_normals": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP, _I, _VP]),          # normals, values of measure.marching_cubes
     "vt_voxel_build": (_I, [_VP, _I, _I, _I, _D, _VP, _VP, _VP, _VP, _VP]),
     "vt_voxel_build_clear": (_I, [_VP, _I, _I, _I, _D, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "vt_voxel_build_clear_flags": (_I, [_VP, _I, _I, _I, _D, _VP, _VP, _VP, _VP, _VP, _SZ, _VP, _VP]),
@@ -443,6 +444,8 @@ SIGNATURES = {
     "vt_mesh_cluster_faces": (_I, [_VP, _I64, _I64, _VP, _I, _VP, _VP, _IP, _IP, _VP, _SZ, _VP]),
     "vt_mesh_cluster_place_workspace_bytes": (_SZ, [_I64]),
     "vt_mesh_cluster_place": (_I, [_VP, _I, _I64, _VP, _I64, _I, _VP, _VP, _I64, _I, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_mesh_normals_workspace_bytes": (_SZ, [_I64, _I64]),
+    "vt_mesh_normals": (_I, [_VP, _I, _I64, _VP, _I64, _I, _VP, _VP, _VP, _SZ, _VP]),                   # trimesh face_normals / vertex_normals
     "vt_winding_tree_default_depth": (_I, [_I64]),
     "vt_winding_tree_workspace_bytes": (_SZ, [_I64, _I64, _I]),
     "vt_winding_tree_count": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _SZ, _VP]),

@@ -51,6 +51,25 @@ class Mesh(namedtuple("Mesh", ["vertices", "faces"])):
         if not double:
             v = v.astype(np.float32)
         vlines = [" ".join(vfmt % x for x in row) for row in v.tolist()]
+        n = self.vertex_normals if isinstance(self, NormalMesh) else None     # a plain Mesh writes what it always wrote
+        if n is not None and ft != "off":
+            n = n.detach().cpu().numpy() if torch.is_tensor(n) else np.asarray(n)
+            n = n.reshape(-1, 3).astype(v.dtype)
+            if len(n) != len(v):
+                raise VtError(f"Mesh.export: {len(n)} vertex normals for {len(v)} vertices")
+            nlines = [" ".join(vfmt % x for x in row) for row in n.tolist()]
+            kind = "double" if double else "float"
+            if ft == "ply":
+                head = ["ply", "format ascii 1.0", f"element vertex {len(v)}"] + [f"property {kind} {c}" for c in ("x", "y", "z", "nx", "ny", "nz")] \
+                    + [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+                body = [a + " " + b for a, b in zip(vlines, nlines)] + ["3 %d %d %d" % tuple(r) for r in f.tolist()]
+            else:
+                head = []
+                body = ["v " + line for line in vlines] + ["vn " + line for line in nlines] \
+                    + ["f %d//%d %d//%d %d//%d" % (a, a, b, b, c, c) for a, b, c in (f + 1).tolist()]
+            with open(file_obj, "w") as fh:
+                fh.write("\n".join(head + body) + "\n")
+            return
         if ft == "off":
             head = ["OFF", f"{len(v)} {len(f)} 0"]
             body = vlines + ["3 %d %d %d" % tuple(r) for r in f.tolist()]
@@ -102,6 +121,21 @@ class Mesh(namedtuple("Mesh", ["vertices", "faces"])):
         from ..utils import mesh_clean
         return mesh_clean.merge_vertices(self, tol=tol, unique_faces=unique_faces)
 
+    def face_normals(self):
+        """Unit face normals [F,3] by the faces' winding; (0,0,0) for a degenerate face."""
+        from ..utils import mesh_clean
+        return mesh_clean.face_normals(self)
+
+    def vertex_normals(self, weight="area"):
+        """Unit vertex normals [V,3] from the geometry, weighted by face 'area' or corner 'angle'."""
+        from ..utils import mesh_clean
+        return mesh_clean.vertex_normals(self, weight=weight)
+
+    def with_vertex_normals(self, weight="area"):
+        """This mesh as a ``NormalMesh`` carrying its geometric vertex normals."""
+        from ..utils import mesh_clean
+        return mesh_clean.with_vertex_normals(self, weight=weight)
+
     def signed_distance_field(self, resolution, loc=None, scale=None, winding='fast', distance='tree'):
         """float64 [resolution]^3: the signed distance to this mesh at the voxel centres of ``VoxelGrid``'s lattice (utils/voxels.py)."""
         from ..utils import voxels
@@ -123,6 +157,35 @@ class Mesh(namedtuple("Mesh", ["vertices", "faces"])):
         """(depth f32 [n, H*W], touch_success bool [n]): the depth images of n sensors pressed against this mesh (utils/render.py)."""
         from ..utils import render
         return render.simulate_touch(self, cam_pos, cam_rot, depth_origin, near=near, threshold=threshold, **kw)
+
+
+class NormalMesh(Mesh):
+    """A ``Mesh`` that carries per-vertex normals.  The tuple is still (vertices, faces): unpacking, indexing and equality are those
+    of ``Mesh``.  Attributes: ``vertex_normals`` [V,3], ``values`` ([V] or None) and ``normals_source`` ('marching_cubes' or
+    'geometry').  ``export`` writes the normals to PLY (nx ny nz) and OBJ (vn, f v//vn); OFF has no place for them.  ``Mesh``'s
+    ``vertex_normals(weight=)`` method is reached as ``geometric_vertex_normals`` here, the name being taken by the attribute."""
+    SOURCES = ("marching_cubes", "geometry")
+
+    def __new__(cls, vertices, faces, vertex_normals=None, values=None, normals_source="geometry"):
+        if vertex_normals is None:
+            raise VtError("NormalMesh: vertex_normals is required (a mesh without normals is a Mesh)")
+        if normals_source not in cls.SOURCES:
+            raise VtError(f"NormalMesh: normals_source must be one of {cls.SOURCES} (got {normals_source!r})")
+        if tuple(vertex_normals.shape) != (vertices.shape[0], 3):
+            raise VtError(f"NormalMesh: vertex_normals must be [{vertices.shape[0]},3] (got {tuple(vertex_normals.shape)})")
+        if values is not None and tuple(values.shape) != (vertices.shape[0],):
+            raise VtError(f"NormalMesh: values must be [{vertices.shape[0]}] (got {tuple(values.shape)})")
+        self = super().__new__(cls, vertices, faces)
+        self.vertex_normals, self.values, self.normals_source = vertex_normals, values, normals_source
+        return self
+
+    def geometric_vertex_normals(self, weight="area"):
+        """Unit vertex normals [V,3] recomputed from the geometry (``Mesh.vertex_normals``)."""
+        from ..utils import mesh_clean
+        return mesh_clean.vertex_normals(self, weight=weight)
+
+    def __reduce__(self):
+        return (NormalMesh, (self.vertices, self.faces, self.vertex_normals, self.values, self.normals_source))
 
 
 _tensor_version = operator.attrgetter("_version")
@@ -264,7 +327,15 @@ class Generator3D(object):
     after the component filter, in the same places as that filter; everything downstream, ``reference_returns``' EMD and Chamfer
     included, sees the simplified mesh.  It costs one host read per probe of the search for the grid (some ten).  The result has at
     most N faces but is not the finest such grid, and its topology is not the input's (``Mesh.components()`` reports what it is).
-    ``None`` (the default) launches nothing.  The Inferencer does not apply it; generate_obj_mesh_sharded refuses it (VtError)."""
+    ``None`` (the default) launches nothing.  The Inferencer does not apply it; generate_obj_mesh_sharded refuses it (VtError).
+
+    ``with_normals`` (config ``generation.with_normals``; the reference's "whether normals should be estimated"): every route that
+    ends in ``extract_mesh`` -- dense, MISE, tactile, the graphed scene -- returns a ``NormalMesh`` whose ``vertex_normals`` and
+    ``values`` are those of scikit-image's ``measure.marching_cubes`` (vt_mc_emit_normals: one launch behind the emit, outside the
+    captured graph; ``normals_source='marching_cubes'``).  The component filter gathers them through its vertex map; after
+    ``simplify_nfaces`` they are recomputed from the geometry, area-weighted (``normals_source='geometry'``, no values);
+    ``generate_hand_mesh`` carries the geometric normals of the MANO vertices.  generate_obj_mesh_sharded refuses it (VtError); the
+    Inferencer ignores it.  ``False`` (the default) launches and returns what it always did."""
 
     EXTRACTIONS = ("dense", "mise")
     COMPONENTS = ("all", "largest", "largest_area", "largest_volume")
@@ -410,11 +481,18 @@ class Generator3D(object):
             raise VtError(f"Generator3D.{what}: the PointConv decoder has no tactile variant (the reference's LocalPointDecoder has "
                           "neither forward_img nor a contact head)")
 
-    def extract_mesh(self, value_grid, level=None):
+    def extract_mesh(self, value_grid, level=None, with_normals=None):
         """``measure.marching_cubes(value_grid, gradient_direction='ascent')`` followed by
-        ``vertices -= nx/2; vertices *= (1+padding)/nx`` (generation.py:270-272), on the device."""
+        ``vertices -= nx/2; vertices *= (1+padding)/nx`` (generation.py:270-272), on the device.  With ``with_normals`` (None: the
+        generator's own flag) the result is a ``NormalMesh`` with scikit-image's normals and values: one more launch."""
         nx = value_grid.shape[0]
-        verts, faces, _ = ops.marching_cubes(value_grid, level, rescale=(nx / 2, (1 + self.padding) / nx))
+        return self._marching_cubes(value_grid, level, (nx / 2, (1 + self.padding) / nx), with_normals)
+
+    def _marching_cubes(self, value_grid, level, rescale, with_normals=None):
+        if self.with_normals if with_normals is None else with_normals:
+            verts, faces, normals, values, _ = ops.mc.marching_cubes_normals(value_grid, level, rescale=rescale)
+            return NormalMesh(verts, faces, vertex_normals=normals, values=values, normals_source="marching_cubes")
+        verts, faces, _ = ops.marching_cubes(value_grid, level, rescale=rescale)
         return Mesh(verts, faces)
 
     # -- whole scene as ONE hipGraph replay (encode + dense decode + marching-cubes count) --------
@@ -572,7 +650,11 @@ class Generator3D(object):
         if self.simplify_nfaces is None or mesh.faces.shape[0] <= self.simplify_nfaces:
             return mesh
         from ..utils import mesh_clean
-        return mesh_clean.simplify(mesh, nfaces=self.simplify_nfaces)
+        simplified = mesh_clean.simplify(mesh, nfaces=self.simplify_nfaces)
+        if isinstance(mesh, NormalMesh) and simplified.faces.shape[0] > 0:
+            # clustering moves the vertices: marching cubes' normals no longer belong to them -- recomputed from the geometry
+            return mesh_clean.with_vertex_normals(simplified, weight="area")
+        return simplified
 
     def _kept_components(self, mesh):
         if not self._filters_components() or mesh.faces.shape[0] == 0:
@@ -582,7 +664,16 @@ class Generator3D(object):
         keep = comps.n_faces >= self.min_component_faces
         if self.components != "all":
             keep = mesh_clean.largest_mask(comps, {"largest": "faces", "largest_area": "area", "largest_volume": "volume"}[self.components], among=keep)
-        return mesh_clean._filtered(mesh.vertices, mesh.faces, comps, keep)
+        if not isinstance(mesh, NormalMesh):
+            return mesh_clean._filtered(mesh.vertices, mesh.faces, comps, keep)
+        # the normals and values of the kept vertices, through the filter's vertex map (the kept vertices keep their order)
+        table = ops.mesh.ComponentTable(comps.n_components, comps.comp_of_vertex, comps.comp_of_face)
+        out = ops.mesh.filter_components(mesh.vertices, mesh.faces, table, keep)
+        kept = out.vertex_map >= 0
+        if out.vertices.shape[0] == 0:
+            return Mesh(out.vertices, out.faces)
+        return NormalMesh(out.vertices, out.faces, vertex_normals=mesh.vertex_normals[kept],
+                          values=None if mesh.values is None else mesh.values[kept], normals_source=mesh.normals_source)
 
     def generate_mesh_graphed(self, inputs):
         """``_generate_mesh_graphed`` (the captured visual branch), then the component filter where one is set."""
@@ -606,10 +697,16 @@ class Generator3D(object):
             ops.mc_echo_arm(g["echo"])                               # the number this replay's scan kernel writes behind the counts
         g["graph"].replay()
         verts, faces, _ = ops.mc_emit(g["vol"], g["ws"], rescale=(nx / 2, (1 + self.padding) / nx), echo=g.get("echo"))
+        if self.with_normals:                                        # one launch behind the emit, outside the captured graph
+            normals, values = ops.mc.mc_emit_normals(g["vol"], g["ws"], verts.shape[0])
+            return NormalMesh(verts, faces, vertex_normals=normals, values=values, normals_source="marching_cubes")
         return Mesh(verts, faces)
 
     def generate_obj_mesh_sharded(self, data, group=None):
         """``_generate_obj_mesh_sharded``; a component filter or ``simplify_nfaces`` is refused before anything is launched."""
+        if self.with_normals:
+            raise VtError("generate_obj_mesh_sharded: with_normals is not built for the sharded route; take the normals of the returned "
+                          "mesh with Mesh.with_vertex_normals(), or ops.mc.marching_cubes_normals of the gathered value grid")
         if self.simplify_nfaces is not None:
             raise VtError("generate_obj_mesh_sharded: simplify_nfaces is not built for the sharded route; simplify the returned mesh with "
                           "Mesh.simplify(nfaces=...)")
@@ -820,6 +917,10 @@ class Generator3D(object):
         centroid = cloud.mean(dim=0)
         m = (cloud - centroid).pow(2).sum(dim=1).sqrt().max()
         v = (v - centroid.double()) / (2.0 * m.double())
+        if self.with_normals:                                        # the 778 MANO vertices: normals of the geometry, area-weighted
+            from ..utils import mesh_clean
+            return NormalMesh(v, c_hand['mano_faces'], vertex_normals=mesh_clean.vertex_normals((v, c_hand['mano_faces'])),
+                              normals_source="geometry")
         return Mesh(v, c_hand['mano_faces'])
 
     def generate_tactile_pc(self, data, fov=60.0):
@@ -1059,8 +1160,7 @@ class Generator3D(object):
                                             self.device)
         self.mise_points_per_level = per_level
         n = values.shape[0]
-        verts, faces, _ = ops.marching_cubes(values, level, rescale=((n - 1) / 2, box / (n - 1)))
-        return Mesh(verts, faces)
+        return self._marching_cubes(values, level, ((n - 1) / 2, box / (n - 1)))
 
     def _setup_vtaco_t2d(self, data, sides=None):
         """The VTacO branch of generate_obj_mesh_wnf (generation.py:202-257): per finger whose touch succeeded, the contact cloud

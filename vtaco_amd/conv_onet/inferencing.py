@@ -253,7 +253,7 @@ class Inferencer(object):
                 logits = ops.decode_fwd_ids(grid, dec._blob(img=True, precision=prec), fid, self._rows(s, k), pts=pts,
                                             padding=dec.padding, precision=prec)
             ops.mise_scatter(s.values, idx, logits.reshape(-1))
-        return gen.extract_mesh(s.values.view(s.nx, s.nx, s.nx))
+        return gen.extract_mesh(s.values.view(s.nx, s.nx, s.nx), with_normals=False)     # (the Inferencer ignores with_normals)
 
     # -- what the tests and tools read --------------------------------------------------------------------------------------
     @property

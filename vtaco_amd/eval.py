@@ -234,26 +234,59 @@ def sample_mesh_surface(verts, faces, n, generator=None):
     return (a[face] * w0 + b[face] * w1 + c[face] * w2).float(), face
 
 
-def mesh_distances(pred_mesh, gt_mesh, n, generator=None, threshold=0.01, distance='brute'):
+def _closest_face(distance, verts, faces, pts):
+    """(d2, face) of ``_distance2``'s call: the same kernels, the same bits, with the index of the closest face kept."""
+    from . import ops
+    if distance == 'brute':
+        cp = ops.metrics.closest_point_mesh(verts.float(), faces, pts, want_point=False)
+    elif distance == 'tree':
+        cp = ops.metrics.closest_point_tree_query(ops.metrics.closest_point_tree_build(verts.float(), faces), pts, want_point=False)
+    else:
+        raise ValueError("distance must be 'brute' or 'tree'")
+    return cp.d2, cp.face
+
+
+def _face_normals(verts, faces):
+    from . import ops
+    return ops.mesh.normals(verts.float().contiguous(), faces.int().contiguous(), vertex=False).face_normals.double()
+
+
+def mesh_distances(pred_mesh, gt_mesh, n, generator=None, threshold=0.01, distance='brute', normals=False):
     """Surface-to-surface distances of two meshes, each (verts [V,3] f32, faces [F,3] int) on the device: ``n`` area-weighted samples
     per mesh (``sample_mesh_surface``), every sample's distance to the OTHER mesh's surface (vt_closest_point_mesh) -- not to its
     vertices, so a dense mesh is not favoured.  Returns floats: 'accuracy' (mean distance of the predicted samples to the ground-truth
     mesh), 'completeness' (the other way), 'chamfer_l1' (their mean), 'f_score' (harmonic mean of the shares of samples within
     ``threshold``, precision and recall; 0 when both are 0).  ``distance='tree'`` takes the same distances from a walk of each mesh's face
-    octree (vt_closest_tree_query: equal bits, far fewer faces per sample on a large mesh)."""
+    octree (vt_closest_tree_query: equal bits, far fewer faces per sample on a large mesh).
+
+    ``normals=True`` adds the normal consistency of the ConvONet evaluation, from the same samples: 'normals_accuracy', the mean of
+    |n_sample . n_closest| over the predicted samples -- n_sample the unit normal of the sampled face, n_closest that of the face of the
+    other mesh the closest point lies on (vt_mesh_normals; a degenerate face counts as 0) --, 'normals_completeness', the same the
+    other way round, and 'normals_consistency', their mean.  The absolute value makes it blind to the orientation of either mesh.  The
+    four other keys are what the default call returns from the same generator state, bit for bit."""
     (pv, pf), (gv, gf) = pred_mesh, gt_mesh
-    sp, _ = sample_mesh_surface(pv, pf, n, generator)
-    sg, _ = sample_mesh_surface(gv, gf, n, generator)
-    acc = torch.sqrt(_distance2(distance, gv, gf, sp))
-    comp = torch.sqrt(_distance2(distance, pv, pf, sg))
+    sp, fp = sample_mesh_surface(pv, pf, n, generator)
+    sg, fg = sample_mesh_surface(gv, gf, n, generator)
+    if normals:
+        (d2_acc, near_g), (d2_comp, near_p) = _closest_face(distance, gv, gf, sp), _closest_face(distance, pv, pf, sg)
+    else:
+        d2_acc, d2_comp = _distance2(distance, gv, gf, sp), _distance2(distance, pv, pf, sg)
+    acc = torch.sqrt(d2_acc)
+    comp = torch.sqrt(d2_comp)
     precision, recall = float((acc <= threshold).double().mean()), float((comp <= threshold).double().mean())
     accuracy, completeness = float(acc.mean()), float(comp.mean())
     f_score = 2 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
-    return {'accuracy': accuracy, 'completeness': completeness, 'chamfer_l1': 0.5 * (accuracy + completeness), 'f_score': f_score}
+    out = {'accuracy': accuracy, 'completeness': completeness, 'chamfer_l1': 0.5 * (accuracy + completeness), 'f_score': f_score}
+    if normals:
+        np_, ng = _face_normals(pv, pf), _face_normals(gv, gf)
+        n_acc = float((np_[fp] * ng[near_g.long()]).sum(dim=1).abs().mean())
+        n_comp = float((ng[fg] * np_[near_p.long()]).sum(dim=1).abs().mean())
+        out.update({'normals_accuracy': n_acc, 'normals_completeness': n_comp, 'normals_consistency': 0.5 * (n_acc + n_comp)})
+    return out
 
 
 def mesh_distances_aligned(pred_mesh, gt_mesh, n, generator=None, threshold=0.01, max_iterations=20, tolerance=1e-3, distance='brute',
-                           registration='brute'):
+                           registration='brute', normals=False):
     """``mesh_distances`` after a rigid registration of the predicted mesh onto the ground truth, so that a pose offset of the prediction
     does not read as shape error.  Both surfaces are sampled exactly as ``mesh_distances`` samples them; ``ops.icp.icp`` maps the
     predicted samples onto the ground-truth samples (vt_icp, float64); its T moves the predicted vertices, per component
@@ -261,7 +294,8 @@ def mesh_distances_aligned(pred_mesh, gt_mesh, n, generator=None, threshold=0.01
     from the same random draws (the generator is put back to where the sampling began, so it ends where one ``mesh_distances`` call
     leaves it), plus 'transform' (4x4 float64 numpy array) and 'icp_iterations' (int, the 0-based index of the last executed iteration).
     ``distance`` is ``mesh_distances``'; ``registration='tree'`` searches the loop's neighbours in an octree over the ground-truth
-    samples (vt_icp_tree): the same transform, bit for bit."""
+    samples (vt_icp_tree): the same transform, bit for bit.  ``normals`` is ``mesh_distances``': the sample normals are those of the moved
+    mesh, that is, rotated with T."""
     from . import ops
     from ._lib import VtError
     if registration not in ('brute', 'tree'):
@@ -277,7 +311,7 @@ def mesh_distances_aligned(pred_mesh, gt_mesh, n, generator=None, threshold=0.01
         generator.set_state(state)
     else:
         torch.cuda.set_rng_state(state, pv.device)
-    out = mesh_distances((moved, pf), gt_mesh, n, generator, threshold, distance=distance)
+    out = mesh_distances((moved, pf), gt_mesh, n, generator, threshold, distance=distance, normals=normals)
     out['transform'] = T.cpu().numpy()
     out['icp_iterations'] = int(fit.iterations)
     return out

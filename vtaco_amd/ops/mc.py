@@ -5,6 +5,9 @@ import torch
 
 from ._base import _lib, VtError, check, dev_ptr, stream_ptr, _c
 
+# what ``from .mc import *`` hands to ``vtaco_amd.ops``; ``mc_emit_normals`` and ``marching_cubes_normals`` are reached as ``ops.mc.*``
+__all__ = ["mc_count", "mc_count_notify", "mc_echo_slot", "mc_echo_release", "mc_count_echo", "mc_echo_arm", "mc_emit", "marching_cubes"]
+
 
 _mc_ws_cache = {}
 
@@ -156,3 +159,32 @@ def marching_cubes(vol, level=None, rescale=None, capacity=None):
         return mc_emit(vol, mc_count(vol, level), rescale, capacity)
     ws, tok = mc_count_notify(vol, level)            # the counts arrive in a page-locked slot: no copy between count and emit
     return mc_emit(vol, ws, rescale, None, token=tok)
+
+
+def mc_emit_normals(vol, ws, n_verts):
+    """The normals [V,3] and values [V] of the vertices ``mc_emit`` numbered (vt_mc_emit_normals): one asynchronous launch behind
+    ``mc_count`` / ``mc_emit`` on the same volume and workspace.  ``n_verts``: the rows to write (the vertex count or a capacity)."""
+    n0, n1, n2 = vol.shape
+    n_verts = int(n_verts)
+    normals = torch.empty((n_verts, 3), dtype=torch.float32, device=vol.device)
+    values = torch.empty(n_verts, dtype=torch.float32, device=vol.device)
+    check(_lib.load().vt_mc_emit_normals(dev_ptr(vol, "vol"), n0, n1, n2, ctypes.c_void_p(ws.data_ptr()), dev_ptr(normals, "normals"),
+                                         dev_ptr(values, "values"), n_verts, stream_ptr()), "vt_mc_emit_normals")
+    return normals, values
+
+
+def marching_cubes_normals(vol, level=None, rescale=None):
+    """``marching_cubes`` with the other half of scikit-image's result: (verts, faces, normals f32 [V,3], values f32 [V], level), as
+    ``measure.marching_cubes(vol, level, gradient_direction='ascent')`` returns them (reference generation.py:270).  The normals are
+    unit, in array-axis order like the vertices, (0,0,0) where scikit-image's sum is zero or not finite; ``rescale`` is a uniform scale
+    and leaves them as they are.  One extra launch behind the emit; the count is read back once, as in ``marching_cubes``."""
+    if vol.dim() != 3:
+        raise VtError("marching_cubes: volume must be [n0,n1,n2]")
+    vol = _c(vol)
+    if torch.cuda.is_current_stream_capturing():
+        raise VtError("marching_cubes_normals: reads the vertex count back; inside a capture use mc_count / mc_emit with a capacity "
+                      "and mc_emit_normals")
+    ws, tok = mc_count_notify(vol, level)
+    verts, faces, lvl = mc_emit(vol, ws, rescale, None, token=tok)
+    normals, values = mc_emit_normals(vol, ws, verts.shape[0])
+    return verts, faces, normals, values, lvl

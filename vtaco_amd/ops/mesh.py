@@ -1,5 +1,5 @@
 """Topology of a triangle mesh (vt_mesh_components, vt_mesh_component_table, vt_mesh_component_stats, vt_mesh_edge_stats, vt_mesh_filter:
-csrc/mesh_topo.hip) and, at the end of the file, its simplification and welding (vt_mesh_cluster, vt_mesh_weld, vt_mesh_cluster_faces,
+csrc/mesh_topo.hip), its normals (vt_mesh_normals: csrc/mesh_normals.hip; ``ops.mesh.normals``) and, at the end of the file, its simplification and welding (vt_mesh_cluster, vt_mesh_weld, vt_mesh_cluster_faces,
 vt_mesh_cluster_place: csrc/mesh_simplify.hip).  A submodule only: callers write ``ops.mesh.components``, ``ops.mesh.component_table``, ``ops.mesh.component_stats``,
 ``ops.mesh.edge_stats``, ``ops.mesh.filter_components``.  faces are int32 [F,3] and vertices float32 or float64 [V,3] device tensors, as
 ``ops.marching_cubes`` returns them; int64 faces are refused, not converted (a conversion would be a torch computation here: the caller
@@ -159,6 +159,35 @@ def filter_components(vertices, faces, table, keep):
                              dev_ptr(out_v, "out_vertices", out_v.dtype), dev_ptr(out_f, "out_faces", I32), dev_ptr(vmap, "vertex_map", I32),
                              ctypes.byref(nv), ctypes.byref(nf), ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "vt_mesh_filter")
     return FilteredMesh(out_v[:nv.value], out_f[:nf.value], vmap)
+
+
+# ---- normals (csrc/mesh_normals.hip) ---------------------------------------------------------------------------------------------------
+WEIGHTS = ("area", "angle")
+MeshNormals = namedtuple("MeshNormals", ["face_normals", "vertex_normals"])
+
+
+def normals(vertices, faces, weight="area", face=True, vertex=True):
+    """MeshNormals(face_normals [F,3], vertex_normals [V,3]) in the vertices' dtype (vt_mesh_normals); ``face`` / ``vertex`` False leaves
+    that one None and its work undone.  Face normals are unit, (0,0,0) for a degenerate face.  A vertex normal is the normalised sum over
+    the vertex's live faces of the raw cross product (``weight='area'``) or of the unit normal times the corner's angle (``'angle'``);
+    (0,0,0) for a vertex that no live face references.  The sums are exact: equal bits from run to run and under any order of the faces.
+    One host read (the status word: a face index outside [0, V) raises)."""
+    what = "mesh.normals"
+    if weight not in WEIGHTS:
+        raise VtError(f"{what}: weight must be one of {WEIGHTS} (got {weight!r})")
+    if not face and not vertex:
+        raise VtError(f"{what}: nothing asked for (face=False, vertex=False)")
+    faces = _faces(what, faces, vertices)
+    vertices = _vertices(what, vertices)
+    V, F, dev = vertices.shape[0], faces.shape[0], faces.device
+    fn = torch.empty((F, 3), dtype=vertices.dtype, device=dev) if face else None
+    vn = torch.empty((V, 3), dtype=vertices.dtype, device=dev) if vertex else None
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_normals_workspace_bytes(V, F), dev)
+    check(lib.vt_mesh_normals(dev_ptr(vertices, "vertices", vertices.dtype), int(vertices.dtype == F64), V, dev_ptr(faces, "faces", I32), F,
+                              WEIGHTS.index(weight), dev_ptr(fn, "face_normals", vertices.dtype), dev_ptr(vn, "vertex_normals", vertices.dtype),
+                              ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "vt_mesh_normals")
+    return MeshNormals(fn, vn)
 
 
 # ---- simplification and welding (csrc/mesh_simplify.hip) ---------------------------------------------------------------------------------

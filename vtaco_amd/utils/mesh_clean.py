@@ -9,6 +9,9 @@ its meshes in ``trimesh.Trimesh`` (``split``, ``area``, ``volume``, ``is_waterti
     simplify(mesh, nfaces=None, resolution=None, placement='quadric') -> Mesh        (csrc/mesh_simplify.hip, as the next two)
     simplify_report(...) -> (Mesh, SimplifyReport)
     merge_vertices(mesh, tol=0.0, unique_faces=False) -> Mesh
+    face_normals(mesh) -> [F,3]                  unit, (0,0,0) for a degenerate face (csrc/mesh_normals.hip, as the next two)
+    vertex_normals(mesh, weight='area') -> [V,3] 'area' or 'angle'; (0,0,0) for a vertex no live face references
+    with_vertex_normals(mesh, weight='area') -> NormalMesh
 
 A mesh is ``generation.Mesh``, any object with ``.vertices`` / ``.faces``, or a ``(vertices, faces)`` pair of device tensors: vertices
 float32 or float64 [V,3], faces int32 [F,3] (int64 faces are converted here).  Components are numbered by their smallest vertex index.
@@ -233,3 +236,33 @@ def merge_vertices(mesh, tol=0.0, unique_faces=False):
     if faces.n_clusters == 0:
         return _empty(v, f)
     return Mesh(m.cluster_place(v, f, clusters, faces.n_clusters, "representative"), faces.faces)
+
+
+# ---- normals (csrc/mesh_normals.hip; tests/mesh_normals_ref.py is the definition) --------------------------------------------------------
+def face_normals(mesh):
+    """Unit face normals [F,3] in the vertices' dtype, by the faces' winding; (0,0,0) for a degenerate face.  [0,3] without faces."""
+    from .. import ops
+    v, f = _parts(mesh)
+    if f.shape[0] == 0:
+        return v.new_zeros((0, 3))
+    return ops.mesh.normals(v, f, vertex=False).face_normals
+
+
+def vertex_normals(mesh, weight="area"):
+    """Unit vertex normals [V,3] in the vertices' dtype: the normalised sum of the vertex's faces' raw cross products (``'area'``, what
+    trimesh's default amounts to up to its sparse-matrix rounding) or of their unit normals times the corner angle (``'angle'``).
+    (0,0,0) for a vertex that no live face references.  Exact sums: the bits do not depend on the order of the faces."""
+    from .. import ops
+    if weight not in ops.mesh.WEIGHTS:
+        raise VtError(f"mesh_clean.vertex_normals: weight must be one of {ops.mesh.WEIGHTS} (got {weight!r})")
+    v, f = _parts(mesh)
+    if f.shape[0] == 0 or v.shape[0] == 0:
+        return torch.zeros_like(v)
+    return ops.mesh.normals(v, f, weight=weight, face=False).vertex_normals
+
+
+def with_vertex_normals(mesh, weight="area"):
+    """The mesh as a ``NormalMesh`` that carries its geometric vertex normals (``normals_source='geometry'``)."""
+    from ..conv_onet.generation import NormalMesh
+    v, f = _parts(mesh)
+    return NormalMesh(v, f, vertex_normals=vertex_normals((v, f), weight=weight), normals_source="geometry")
