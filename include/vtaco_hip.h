@@ -1802,6 +1802,48 @@ int vt_ray_tree_query(const void *tree, size_t tree_bytes, const void *side, siz
 int vt_camera_rays(const double *pose, int n_images, int width, int height, double fov_deg, double *origins, double *dirs, void *stream);
 int vt_depth_from_hits(const double *s, const double *depth_origin, int64_t n_pixels, int64_t N, double near, float *depth, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------ */
+/* The field's second-order jet and mesh refinement on it (csrc/field_jet.hip, csrc/refine.hip; DESIGN.md section "field_jet / refine";  */
+/* tests/refine_ref.py states both in float64 autograd).  Stands where the Convolutional Occupancy Networks generator's refine_mesh     */
+/* differentiates the decoder twice (generation.refinement_step).  The 32 / 32 / 5 plain decoder only: C != 32 is VT_ERR_UNSUPPORTED.   */
+/*   vt_decode_jet           jet [B*N][8] f32 = (f, f_x, f_y, f_z, f_xy, f_xz, f_yz, 0) at pts [B][N][3]: the logit, its gradient with      */
+/*                           respect to the point and the three mixed second derivatives (the pure ones are zero: the field is           */
+/*                           multilinear inside a cell between ReLU kinks).  An axis whose coordinate the normalisation clamps has zero  */
+/*                           derivatives.  blob / blob_t: vt_decoder_pack / vt_decoder_pack_t of the plain decoder.  One kernel, exact-   */
+/*                           f32 matrix core; f is vt_decode_fwd's logit bit for bit.                                                     */
+/*   vt_decode_jet_composed  the same numbers, bit for bit, from vt_decode_fwd (save) + vt_decode_bwd_dc (grad_out = 1) + one gather     */
+/*                           kernel.  workspace: vt_decode_jet_composed_workspace_bytes(B, N) (B = 1 runs in passes of 2^17 points).      */
+/*   vt_refine_sample        pts [F][3] = (eps_0 v_0 + eps_1 v_1) + eps_2 v_2 per face; eps_in [F][3] given, or NULL: eps [F][3] is drawn   */
+/*                           as Dirichlet(1/2,1/2,1/2) from a counter hash of (seed, step, face).  eps may be eps_in.                     */
+/*   vt_refine_face_grad     the vertex gradient of L = mean (sigmoid(f) - threshold)^2 + normal_weight mean |n_face - n_target|^2,       */
+/*                           n_target = -g / (|g| + 1e-10), g = grad sigmoid(f), differentiated through g: added into accum as exact      */
+/*                           fixed-point sums (vt_refine_accum_bytes(V) bytes, zero before the first call; equal bits under any face      */
+/*                           order).  terms NULL or [F][2] f32: (sigmoid(f) - threshold)^2 and |n_face - n_target|^2 per face.            */
+/*   vt_refine_step          grad (NULL or [V][3] f32) = the sums, which it zeroes; sq = alpha sq + (1 - alpha) grad^2;                    */
+/*                           verts -= lr grad / (sqrt(sq) + eps): torch.optim.RMSprop.                                                     */
+/*   vt_refine               `steps` iterations of sample -> jet -> face_grad -> step (RMSprop alpha 0.99, eps 1e-8) on one stream, no    */
+/*                           host read.  Iteration i draws with step = first_step + i; eps_given (steps <= 1) replaces the draw.  sq      */
+/*                           [V][3] is the caller's (zeros at the start).  composed_jet != 0 takes vt_decode_jet_composed.  terms NULL or  */
+/*                           [steps][F][2].  workspace: vt_refine_workspace_bytes(V, F, composed_jet).                                     */
+/* A face with an index outside [0, V) is never dereferenced and contributes nothing.  All are asynchronous and read nothing back.       */
+int vt_decode_jet(const float *grid_cl, int B, int R, int C, const float *pts, int64_t N, const float *blob, const float *blob_t,
+                  double padding, float *jet, void *stream);
+size_t vt_decode_jet_composed_workspace_bytes(int B, int64_t N);
+int vt_decode_jet_composed(const float *grid_cl, int B, int R, int C, const float *pts, int64_t N, const float *blob, const float *blob_t,
+                           double padding, float *jet, void *workspace, size_t workspace_bytes, void *stream);
+int vt_refine_sample(const float *verts, int64_t V, const int32_t *faces, int64_t F, const float *eps_in, uint64_t seed, uint64_t step,
+                     float *eps, float *pts, void *stream);
+size_t vt_refine_accum_bytes(int64_t V);
+int vt_refine_face_grad(const float *verts, int64_t V, const int32_t *faces, int64_t F, const float *eps, const float *jet,
+                        double threshold, double normal_weight, float *terms, void *accum, size_t accum_bytes, void *stream);
+int vt_refine_step(float *verts, int64_t V, void *accum, size_t accum_bytes, float *sq, double lr, double alpha, double eps, float *grad,
+                   void *stream);
+size_t vt_refine_workspace_bytes(int64_t V, int64_t F, int composed_jet);
+int vt_refine(const float *grid_cl, int R, int C, float *verts, int64_t V, const int32_t *faces, int64_t F, const float *blob,
+              const float *blob_t, double padding, double threshold, double normal_weight, double lr, int steps, uint64_t seed,
+              uint64_t first_step, const float *eps_given, float *sq, int composed_jet, float *terms, void *workspace, size_t workspace_bytes,
+              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,7 @@ class TactileUnetGrads(ctypes.Structure):
 # parses the header and checks that every declared symbol is exported and listed here)
 _VP, _I, _I64, _F, _D, _SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
 _IP = ctypes.POINTER(ctypes.c_int)
+_U64 = ctypes.c_uint64
 SIGNATURES = {
     "vt_abi_version": (_I, []),
     "vt_last_error": (ctypes.c_char_p, []),
@@ -460,6 +461,15 @@ SIGNATURES = {
     "vt_ray_tree_query": (_I, [_VP, _SZ, _VP, _SZ, _I64, _I, _VP, _VP, _I64, _VP, _I64, _D, _D, _VP, _VP, _VP, _VP, _VP]),
     "vt_camera_rays": (_I, [_VP, _I, _I, _I, _D, _VP, _VP, _VP]),
     "vt_depth_from_hits": (_I, [_VP, _VP, _I64, _I64, _D, _VP, _VP]),
+    "vt_decode_jet": (_I, [_VP, _I, _I, _I, _VP, _I64, _VP, _VP, _D, _VP, _VP]),                         # generation.refinement_step
+    "vt_decode_jet_composed_workspace_bytes": (_SZ, [_I, _I64]),
+    "vt_decode_jet_composed": (_I, [_VP, _I, _I, _I, _VP, _I64, _VP, _VP, _D, _VP, _VP, _SZ, _VP]),
+    "vt_refine_sample": (_I, [_VP, _I64, _VP, _I64, _VP, _U64, _U64, _VP, _VP, _VP]),
+    "vt_refine_accum_bytes": (_SZ, [_I64]),
+    "vt_refine_face_grad": (_I, [_VP, _I64, _VP, _I64, _VP, _VP, _D, _D, _VP, _VP, _SZ, _VP]),
+    "vt_refine_step": (_I, [_VP, _I64, _VP, _SZ, _VP, _D, _D, _D, _VP, _VP]),
+    "vt_refine_workspace_bytes": (_SZ, [_I64, _I64, _I]),
+    "vt_refine": (_I, [_VP, _I, _I, _VP, _I64, _VP, _I64, _VP, _VP, _D, _D, _D, _D, _I, _U64, _U64, _VP, _VP, _I, _VP, _VP, _SZ, _VP]),
 }
 
 _lib = None

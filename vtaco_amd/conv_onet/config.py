@@ -63,7 +63,7 @@ def get_generator(model, cfg, device, **kwargs):
     g = cfg['generation']
     return Generator3D(model, device=device, threshold=cfg['test']['threshold'], resolution0=g['resolution_0'],
                        upsampling_steps=g['upsampling_steps'], sample=g.get('use_sampling', False),
-                       refinement_step=g.get('refinement_step', 0), simplify_nfaces=g.get('simplify_nfaces'),
+                       refinement_step=g.get('refinement_step', 0), refine_sampler=g.get('refine_sampler', 'device'), simplify_nfaces=g.get('simplify_nfaces'),
                        with_normals=bool(g.get('with_normals', False)),
                        input_type=cfg['data']['input_type'], padding=cfg['data']['padding'],
                        with_img=cfg['model'].get('with_img', False), encode_t2d=cfg['model'].get('encoder_t2d', False),

@@ -136,6 +136,11 @@ class Mesh(namedtuple("Mesh", ["vertices", "faces"])):
         from ..utils import mesh_clean
         return mesh_clean.with_vertex_normals(self, weight=weight)
 
+    def refine(self, generator, c, steps=None, eps=None, seed=0):
+        """This mesh after ``steps`` refinement iterations against ``generator``'s field on the encoder output ``c``
+        (``Generator3D.refine_mesh``): same faces, moved vertices."""
+        return generator.refine_mesh(self, c, steps=steps, eps=eps, seed=seed)
+
     def signed_distance_field(self, resolution, loc=None, scale=None, winding='fast', distance='tree'):
         """float64 [resolution]^3: the signed distance to this mesh at the voxel centres of ``VoxelGrid``'s lattice (utils/voxels.py)."""
         from ..utils import voxels
@@ -335,10 +340,26 @@ class Generator3D(object):
     captured graph; ``normals_source='marching_cubes'``).  The component filter gathers them through its vertex map; after
     ``simplify_nfaces`` they are recomputed from the geometry, area-weighted (``normals_source='geometry'``, no values);
     ``generate_hand_mesh`` carries the geometric normals of the MANO vertices.  generate_obj_mesh_sharded refuses it (VtError); the
-    Inferencer ignores it.  ``False`` (the default) launches and returns what it always did."""
+    Inferencer ignores it.  ``False`` (the default) launches and returns what it always did.
+
+    ``refinement_step`` (config ``generation.refinement_step``; the Convolutional Occupancy Networks generator's ``refine_mesh``): a
+    positive integer N runs N RMSprop iterations (torch's defaults, lr 1e-4) on the vertices of the finished object mesh -- after the
+    component filter and ``simplify_nfaces``, upstream's order -- in generate_obj_mesh_wnf's visual route, dense and MISE.  Every
+    iteration draws one point per face, pulls the occupancy there to ``threshold`` and the face normal to the negative normalised
+    gradient of the occupancy, differentiating through that gradient: ``refine_mesh`` below, csrc/field_jet.hip and csrc/refine.hip,
+    six launches per iteration and no host read.  The encoder runs once more, eagerly, for the feature volume (a graphed route keeps
+    its own inside the graph).  ``refine_sampler='device'`` (the default) draws the points' weights in the kernel from a counter hash
+    of (seed 0, step, face); ``'numpy'`` draws ``np.random.dirichlet((0.5, 0.5, 0.5), size=F)`` from numpy's global generator once per
+    step and uploads it, exactly as upstream.  With ``with_normals`` the normals are recomputed from the refined geometry
+    (``normals_source='geometry'``, no values); ``reference_returns`` measures the refined mesh.  Refused (VtError, in the constructor):
+    a negative or non-integer value, and with N > 0 the tactile routes (``with_img``, ``encode_t2d``), the attention decoder, plane
+    features, the PointConv baseline and decoder shapes other than hidden 32 / c_dim 32 / 5 blocks (the jet kernel's shape);
+    generate_mesh_graphed, generate_obj_mesh_sharded and generate_obj_mesh_tactile refuse N > 0 when called.  The Inferencer ignores
+    it.  ``0`` (the default) launches nothing and returns what it always did."""
 
     EXTRACTIONS = ("dense", "mise")
     COMPONENTS = ("all", "largest", "largest_area", "largest_volume")
+    REFINE_SAMPLERS = ("device", "numpy")
 
     MAX_SCENE_GRAPHS = 4
     FUSED_CHUNKS_PER_CALL = 256          # attention_local: chunks of points_batch_size points evaluated per launch sequence (see _fused_chunks_per_call)
@@ -349,7 +370,11 @@ class Generator3D(object):
                  resolution0=16, upsampling_steps=3, with_normals=False, padding=0.1, sample=False,
                  input_type=None, vol_info=None, vol_bound=None, simplify_nfaces=None, alpha=0.2,
                  with_img=False, encode_t2d=False, decode_precision="f16x3", depth_origin=None, reference_returns=False,
-                 extraction="dense", components="all", min_component_faces=0):
+                 extraction="dense", components="all", min_component_faces=0, refine_sampler="device"):
+        if isinstance(refinement_step, bool) or not isinstance(refinement_step, numbers.Integral) or refinement_step < 0:
+            raise VtError(f"Generator3D: refinement_step must be an integer >= 0 (got {refinement_step!r})")
+        if refine_sampler not in self.REFINE_SAMPLERS:
+            raise VtError(f"Generator3D: refine_sampler must be one of {self.REFINE_SAMPLERS} (got {refine_sampler!r})")
         if components not in self.COMPONENTS:
             raise VtError(f"Generator3D: components must be one of {self.COMPONENTS} (got {components!r})")
         if int(min_component_faces) != min_component_faces or min_component_faces < 0:
@@ -378,7 +403,7 @@ class Generator3D(object):
         # decoder's own ``precision`` attribute (default "f32").
         self.decode_precision = decode_precision
         self.points_batch_size = points_batch_size
-        self.threshold, self.refinement_step = threshold, refinement_step
+        self.threshold, self.refinement_step, self.refine_sampler = threshold, int(refinement_step), refine_sampler
         self.device = device
         self.resolution0, self.upsampling_steps = resolution0, upsampling_steps
         self.with_normals, self.input_type, self.padding, self.sample = with_normals, input_type, padding, sample
@@ -390,6 +415,52 @@ class Generator3D(object):
         self.vol_bound = vol_bound
         if input_type == 'pointcloud_crop':
             raise VtError("Generator3D: crop / sliding-window mode is not built (no shipped config uses it)")
+        if self.refinement_step > 0:
+            self._refuse_refinement_config()
+
+    # -- refinement_step: RMSprop on the vertices against the field's jet -----------
+    def _refuse_refinement_config(self):
+        """What refinement_step > 0 cannot be combined with, said before anything is launched."""
+        if self.with_img or self.encode_t2d:
+            raise VtError("Generator3D(refinement_step > 0): not built for the tactile routes (with_img / encode_t2d): the field there "
+                          "also depends on the finger features assigned to each point, and the jet kernel differentiates the plain decoder")
+        self._refuse_planes("refinement_step > 0", "the jet kernel differentiates the trilinear sample of a feature volume")
+        self._refuse_point("refinement_step > 0", "its features are sampled from a point cloud, not a feature volume")
+        ops.refine.refine_check(getattr(self.model, "decoder", None))
+
+    def _refuse_refinement(self, what, instead):
+        if self.refinement_step > 0:
+            raise VtError(f"Generator3D.{what}: refinement_step is not built for this route; {instead}")
+
+    def refine_mesh(self, mesh, c, steps=None, eps=None, seed=0):
+        """Upstream's ``refine_mesh(mesh, occ_hat, c)`` without the unused ``occ_hat``: ``steps`` (None: ``refinement_step``) RMSprop
+        iterations on the vertices against the decoder's field on the encoder output ``c`` (the feature volume, or the dict that holds
+        it alone).  ``eps`` [steps,F,3]: the face points' weights instead of a draw; ``seed``: the device sampler's.  Returns a Mesh
+        with the same faces and float32 vertices -- a NormalMesh with the normals of the refined geometry where ``mesh`` is one."""
+        steps = self.refinement_step if steps is None else int(steps)
+        dec = self.model.decoder
+        ops.refine.refine_check(dec)
+        if isinstance(c, (tuple, list)):
+            raise VtError("Generator3D.refine_mesh: the PointConv baseline's (cloud, features) pair is not a feature volume")
+        grid = dec._grid_of(c, "refine_mesh") if isinstance(c, dict) else c
+        if steps <= 0 or mesh.faces.shape[0] == 0:
+            return mesh
+        verts = ops.refine.refine(mesh.vertices.float(), mesh.faces, grid, dec, steps, self.threshold, dec.padding, eps=eps, seed=seed,
+                           sampler=self.refine_sampler)
+        out = Mesh(verts, mesh.faces)
+        if isinstance(mesh, NormalMesh):
+            from ..utils import mesh_clean
+            return mesh_clean.with_vertex_normals(out, weight="area")
+        return out
+
+    def _refined(self, mesh, data):
+        """generate_obj_mesh_wnf's refinement: the scene encoded once more, eagerly, for its feature volume."""
+        if mesh.faces.shape[0] == 0:
+            return mesh
+        self._eval_mode()
+        with torch.no_grad():
+            c = self.model.encode_inputs(data.get('inputs').to(self.device))
+        return self.refine_mesh(mesh, c)
 
     # -- reference API: arbitrary points, chunked, result on the CPU ---------------
     def eval_points(self, p, c=None, c_img_all=None, vol_bound=None, **kwargs):
@@ -677,6 +748,7 @@ class Generator3D(object):
 
     def generate_mesh_graphed(self, inputs):
         """``_generate_mesh_graphed`` (the captured visual branch), then the component filter where one is set."""
+        self._refuse_refinement("generate_mesh_graphed", "generate_obj_mesh_wnf refines behind the same graph replay")
         return self._clean(self._generate_mesh_graphed(inputs))
 
     @_range_guarded
@@ -704,6 +776,7 @@ class Generator3D(object):
 
     def generate_obj_mesh_sharded(self, data, group=None):
         """``_generate_obj_mesh_sharded``; a component filter or ``simplify_nfaces`` is refused before anything is launched."""
+        self._refuse_refinement("generate_obj_mesh_sharded", "refine the returned mesh with Mesh.refine(generator, c)")
         if self.with_normals:
             raise VtError("generate_obj_mesh_sharded: with_normals is not built for the sharded route; take the normals of the returned "
                           "mesh with Mesh.with_vertex_normals(), or ops.mc.marching_cubes_normals of the gathered value grid")
@@ -756,6 +829,7 @@ class Generator3D(object):
 
     def generate_obj_mesh_tactile(self, data, finger_feats, anchors, success, mode='within', radius=None, count=None):
         """``_generate_obj_mesh_tactile``, then the component filter where one is set."""
+        self._refuse_refinement("generate_obj_mesh_tactile", "the field there also depends on the finger features assigned to each point")
         return self._clean(self._generate_obj_mesh_tactile(data, finger_feats, anchors, success, mode=mode, radius=radius, count=count))
 
     @_range_guarded
@@ -956,6 +1030,8 @@ class Generator3D(object):
         point cloud [1,T,3].  Returns Mesh(vertices [V,3] f32, faces [F,3] i32) on the device -- or, with
         ``reference_returns``, (mesh, emd, cd) as the reference does (see reference_metrics)."""
         mesh = self._clean(self._generate_obj_mesh(data, c_img_all))
+        if self.refinement_step > 0:
+            mesh = self._refined(mesh, data)
         if not self.reference_returns:
             return mesh
         emd, cd = self.reference_metrics(mesh, data)     # outside the range guard: the metrics are of the scene it kept

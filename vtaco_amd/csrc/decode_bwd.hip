@@ -18,15 +18,7 @@
 
 namespace {
 
-// ---- transposed-weight blob (floats) ---------------------------------------------------
-// 16 layers x [16 k-steps][64 lanes]:  0..4 fc_c{i}^T (output in gather layout)
-//                                      5..9 fc_1{i}^T, 10..14 fc_0{i}^T (accumulator layout)
-//                                      15   fc_p_img[:,3:]^T (gather layout)
-// then fc_out.weight fragment [2][16] and fc_out_contact.weight fragment [2][16] (accumulator layout; zeros without a contact head)
-constexpr int VT_OFFT_OUT = 16 * 1024;
-constexpr int VT_OFFT_OUT2 = VT_OFFT_OUT + 32;
-constexpr int VT_BLOBT_FLOATS = VT_OFFT_OUT2 + 32;
-
+// (the transposed-weight blob's layout, VT_OFFT_* / VT_BLOBT_FLOATS: decode_common.h)
 struct PackArgs {
     vt_decoder_params p;
     float *blob;

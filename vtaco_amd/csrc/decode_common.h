@@ -371,4 +371,13 @@ __device__ __forceinline__ Tri tri_setup(float px, float py, float pz, float div
 
 __device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
+// ---- transposed-weight blob (floats; vt_decoder_pack_t, read by decode_bwd.hip and field_jet.hip) --------
+// 16 layers x [16 k-steps][64 lanes]:  0..4 fc_c{i}^T (output in gather layout)
+//                                      5..9 fc_1{i}^T, 10..14 fc_0{i}^T (accumulator layout)
+//                                      15   fc_p_img[:,3:]^T (gather layout)
+// then fc_out.weight fragment [2][16] and fc_out_contact.weight fragment [2][16] (accumulator layout; zeros without a contact head)
+constexpr int VT_OFFT_OUT = 16 * 1024;
+constexpr int VT_OFFT_OUT2 = VT_OFFT_OUT + 32;
+constexpr int VT_BLOBT_FLOATS = VT_OFFT_OUT2 + 32;
+
 }  // namespace
