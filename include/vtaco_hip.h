@@ -148,6 +148,34 @@ int vt_decode_fwd_f16f8(const float *grid_cl, int B, int R, int C, int64_t N,
                         const float *c_img, const unsigned char *finger_ids, const float *finger_feats, int F,
                         const float *blob_f16f8, double padding, float *out, void *stream);
 
+/* Which kernel form a lattice decode of this shape takes (host only: nothing is launched, no GPU   */
+/* call is made; no reference counterpart).  The same rule vt_decode_fwd, vt_decode_fwd_ids,          */
+/* vt_decode_fwd_bf16x3, vt_decode_fwd_f16x3 and vt_decode_fwd_f16f8 dispatch by, the environment's   */
+/* A/B knobs included, so a test can confirm that a case runs the kernel it means to:                 */
+/*   VT_LATTICE_LINEAR   tiles of 32 consecutive lattice indices, direct gather (any nx, any range)  */
+/*   VT_LATTICE_BRICK    2 x 4 x 4 point bricks, direct gather: nx % 4 == 0, first and N multiples    */
+/*                       of 2 nx^2 (a slab of whole x-plane pairs)                                     */
+/*   VT_LATTICE_STAGED   bricks with the 3 x 4 x 4 voxel footprint staged in LDS: R >= 4, nx <= 512,  */
+/*                       s = (R-1) box / ((nx-1) divisor) < 0.66 voxels per lattice step, LDS fits    */
+/*   VT_LATTICE_STAGED2  2 x 4 x 8 double bricks, 3 x 4 x 6 footprint: nx % 8 == 0, R >= 6, s < 0.55, */
+/*                       no contact head                                                               */
+/*   VT_LATTICE_STAGED3  the slot-pipelined double-brick kernel of the half-precision forms            */
+/* precision: VT_PRECISION_F32 / _BF16X3 / _F16X3 / _F16F8; want_contact: the call gives out2;        */
+/* have_c_direct: the features are given (vt_decode_mlp_fwd*), no grid is sampled.  Returns the form, */
+/* or VT_ERR_INVALID / VT_ERR_UNSUPPORTED where the launcher would refuse the call (C != 32, nx < 2,  */
+/* a range outside the lattice, an f16f8 slab vt_decode_f16f8_covers does not cover).                  */
+#define VT_LATTICE_LINEAR  0
+#define VT_LATTICE_BRICK   1
+#define VT_LATTICE_STAGED  2
+#define VT_LATTICE_STAGED2 3
+#define VT_LATTICE_STAGED3 4
+#define VT_PRECISION_F32    0
+#define VT_PRECISION_BF16X3 1
+#define VT_PRECISION_F16X3  2
+#define VT_PRECISION_F16F8  3
+int vt_decode_lattice_form(int R, int C, int lattice_nx, float lattice_box, int64_t lattice_first, int64_t N, double padding,
+                           int precision, int want_contact, int have_c_direct);
+
 /* Range guard of the half-precision decodes (vt_decode_fwd_f16x3 / _f16f8): their hi operand     */
 /* saturates at 65504 (round toward zero: never an infinity), after which the logits silently lose  */
 /* parity.  Every launch samples its relu'd hi operands (two of a lane's sixteen channels, every     */

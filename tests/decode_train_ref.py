@@ -137,11 +137,12 @@ def forward32(sd, pts, grid, c_img=None, contact=False, c=None, padding=0.1):
     return forward(sd, pts, grid, c_img, contact, c, padding, torch.float32)
 
 
-def forward_bound(sd, pts, grid, c_img=None, contact=False, c=None, padding=0.1):
+def forward_bound(sd, pts, grid, c_img=None, contact=False, c=None, padding=0.1, cb=None):
     """The magnitude sums of :func:`forward64`'s results, in its layout.  Each is the sum of |terms| of the ONE sum that makes the tensor
     from the float64 values of its inputs: sum_k |w_k grid_k| for c, sum |W| relu(x) + |b| for h_i, and for the residual stream x_i every
     term added to it so far (fc_p, the fc_c's, the fc_1's and the biases; the kernels keep it in one accumulator).  Nothing is propagated
-    through a second matrix: a bound run through all five blocks over |W| grows by orders of magnitude and would gate nothing."""
+    through a second matrix: a bound run through all five blocks over |W| grows by orders of magnitude and would gate nothing.
+    ``cb`` with ``c``: the magnitude sum of the sampling that made ``c``, where the caller kept it (|c| otherwise)."""
     dt = torch.float64
     img = c_img is not None
     P, A = _params(sd, img, dt), _params(sd, img, dt, absolute=True)
@@ -151,7 +152,7 @@ def forward_bound(sd, pts, grid, c_img=None, contact=False, c=None, padding=0.1)
         c, cb = sample(grid.detach().to(dt), idx, w), sample(grid.detach().to(dt).abs(), idx, w)
     else:
         c = c.detach().to(dt)
-        cb = c.abs()
+        cb = c.abs() if cb is None else cb.detach().to(dt)
     x = pf @ P["Wp"][:, :3].t() + P["bp"] + c @ P["Wc"][0].t() + P["bc"][0]
     bx = pf.abs() @ A["Wp"][:, :3].t() + A["bp"] + cb @ A["Wc"][0].t() + A["bc"][0]
     if img:

@@ -227,6 +227,7 @@ SIGNATURES = {
     "vt_decode_mlp_fwd_wide_train": (_I, [_VP, _I, _I, _VP, _I64, _VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "vt_decode_mlp_bwd_wide": (_I, [_I, _I, _VP, _I64, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "vt_decode_f16f8_covers": (_I, [_I, _I, _I, _F, _I64, _I64, _D]),
+    "vt_decode_lattice_form": (_I, [_I, _I, _I, _F, _I64, _I64, _D, _I, _I, _I]),
     "vt_decode_fwd_f16f8": (_I, [_VP, _I, _I, _I, _I64, _I, _F, _I64, _VP, _VP, _VP, _I, _VP, _D, _VP, _VP]),
     "vt_decoder_pack_t": (_I, [ctypes.POINTER(DecoderParams), _VP, _SZ, _VP]),
     "vt_decode_save_bytes": (_SZ, [_I64]),

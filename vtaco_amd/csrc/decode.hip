@@ -1116,6 +1116,11 @@ int vt_grid_from_channels_last(const float *src, float *dst, int B, int C, int D
 }  // extern "C"
 #endif  // !VT_DECODE_F16_TU
 
+// voxels per lattice step: s = (R-1) * box / ((nx-1) * divisor), the divisor rounded to f32 as the kernels hold it
+static double lattice_step_voxels(int R, int nx, float box, double padding) {
+    return (double)(R - 1) * (double)box / ((double)(nx - 1) * (double)(float)(1.0 + padding + 10e-4));
+}
+
 #ifdef VT_DECODE_F16_TU
 // the slot-pipelined lattice kernels (decode_st3.h) cover: whole 2 x 4 x 8 double bricks (nx % 8 == 0, a slab of x-plane pairs),
 // less than 0.55 voxels per lattice step (the 3 x 4 x 6 footprint), blob + tables + eight images within the CU's 160 KiB
@@ -1146,9 +1151,6 @@ static int st3_launch(const DecodeArgs &a_in, int variant, void *stream) {
     else hipLaunchKernelGGL(decode_fwd_staged3_kernel<3>, dim3((unsigned)blocks), dim3(ST3_THREADS), lds, (hipStream_t)stream, a);
     return vt_check(hipGetLastError(), "vt_decode_fwd");
 }
-static double lattice_step_voxels(int R, int nx, float box, double padding) {
-    return (double)(R - 1) * (double)box / ((double)(nx - 1) * (double)(float)(1.0 + padding + 10e-4));
-}
 // vt_sample_grid over a lattice slab the staged double-brick kernel covers (whole x-plane pairs, nx % 8 == 0, < 0.55 voxels per
 // step): the gather of decode_fwd_staged3_kernel alone -- footprints by LDS-DMA, corners from LDS -- writing the features.  Same
 // corner and FMA order as sample_grid_kernel: the same bits.  *covered = 0: not such a slab, nothing launched.
@@ -1171,6 +1173,48 @@ int vt_st3_sample_lattice(const float *grid_cl, int B, int R, int C, int64_t N, 
     return st3_launch(a, 3, stream);
 }
 #endif
+
+// ---- which kernel form a lattice decode takes --------------------------------------------------------------------------
+// The one rule behind decode_launch, vt_decode_fwd_f16f8 and the read-only query vt_decode_lattice_form (host code, no GPU call).
+// precision: VT_PRECISION_* (0 exact f32, 1 split-bf16, 2 split-f16, 3 f16f8); contact: the call gives out2; c_direct: features
+// given, no grid sampled; save: the training forward.  The range is taken as valid (the launchers check it first).
+//   linear   tiles of 32 consecutive lattice indices, direct gather: whatever the rest does not take
+//   brick    2 x 4 x 4 point bricks, direct gather: inference, nx % 4 == 0, first and N multiples of 2 nx^2 (x-plane pairs)
+//   staged   bricks whose 3 x 4 x 4 voxel footprint is staged in LDS: a sampled grid of R >= 4, nx <= 512, voxels per lattice
+//            step s = (R-1) * box / ((nx-1) * divisor) < 0.66 (the footprint bound is 2/3; 0.496 at 128^3 / R = 64), and
+//            blob + four-entry table + twelve images within the CU's 160 KiB
+//   staged2  2 x 4 x 8 double bricks, 3 x 4 x 6 footprint: staged's conditions and nx % 8 == 0, R >= 6, s < 0.55, no contact
+//            head, blob + table + eight images + tail within 160 KiB
+//   staged3  the slot-pipelined double-brick kernel (decode_st3.h), split-f16 and f16f8 only: st3_covers (staged2's bounds
+//            with its five-entry table).  f16f8 has no other form: what vt_decode_f16f8_covers refuses is VT_ERR_UNSUPPORTED
+// A/B knobs for tests and benches, read once per process: VTACO_DECODE_DIRECT (no staged form), VTACO_DECODE_NO_PAIR (no
+// double-brick form), VTACO_DECODE_ST3=0 (split-f16 falls back to the compiler-scheduled staged2).  f16f8 ignores them.
+static int decode_lattice_form(int precision, int R, int nx, float box, int64_t first, int64_t N, double padding,
+                               bool contact, bool c_direct, bool save) {
+    const int64_t pair = 2ll * nx * nx;                                // two x-planes
+    const double s_vox = lattice_step_voxels(R, nx, box, padding);
+    if (precision == VT_PRECISION_F16F8) {
+#ifdef VT_DECODE_F16_TU
+        if (nx >= 8 && N > 0 && first % pair == 0 && N % pair == 0 && st3_covers(nx, R, s_vox)) return VT_LATTICE_STAGED3;
+#endif
+        return VT_ERR_UNSUPPORTED;
+    }
+    if (save || (nx & 3) != 0 || first % pair != 0 || N % pair != 0) return VT_LATTICE_LINEAR;
+    static const bool force_direct = getenv("VTACO_DECODE_DIRECT") != nullptr;
+    if (force_direct || R < 4 || nx > 512 || c_direct) return VT_LATTICE_BRICK;
+    const size_t lds_st = ((size_t)VT_BLOB_FLOATS + 4u * (size_t)nx + (size_t)(ST_THREADS / 64) * ST_WAVE_FLOATS) * sizeof(float);
+    const size_t lds_st2 = ((size_t)VT_BLOB_FLOATS + 4u * (size_t)nx) * sizeof(float) + (size_t)(ST2_THREADS / 64) * ST2_WAVE_BYTES + VT_TAIL_LDS_BYTES;
+    static const bool no_pair = getenv("VTACO_DECODE_NO_PAIR") != nullptr;
+#ifdef VT_DECODE_F16_TU
+    if (precision == VT_PRECISION_F16X3) {
+        static const bool no_st3 = getenv("VTACO_DECODE_ST3") != nullptr && atoi(getenv("VTACO_DECODE_ST3")) == 0;
+        if (!no_st3 && !no_pair && !contact && st3_covers(nx, R, s_vox)) return VT_LATTICE_STAGED3;
+    }
+#endif
+    if (!no_pair && !contact && (nx & 7) == 0 && R >= 6 && s_vox > 0.0 && s_vox < 0.55 && lds_st2 <= 160u * 1024u) return VT_LATTICE_STAGED2;
+    if (s_vox > 0.0 && s_vox < 0.66 && lds_st <= 160u * 1024u) return VT_LATTICE_STAGED;
+    return VT_LATTICE_BRICK;
+}
 
 // P: 0 exact f32, 1 split-bf16, 2 split-f16 (the dense layers; decode_common.h)
 template <int P>
@@ -1201,29 +1245,20 @@ static int decode_launch(const float *grid_cl, const float *c_direct, int B, int
     a.N = (uint32_t)N; a.total = (uint32_t)((int64_t)B * N); a.lattice_first = (uint32_t)lattice_first;
     a.R = R; a.nx = lattice_nx; a.box = lattice_box;
     a.divisor = (float)(1.0 + padding + 10e-4);   // src/common.py:302, rounded to f32 as torch does
-    if (!pts && !save && (lattice_nx & 3) == 0) {
-        const int64_t pair = 2ll * lattice_nx * lattice_nx;            // two x-planes
-        if (lattice_first % pair == 0 && N % pair == 0) a.brick = 1;
-    }
-    // LDS-staged gather (decode_fwd_staged_kernel) when the brick footprint is bounded by 3 x 4 x 4 voxels:
-    // voxels per lattice step s = (R-1) * box / ((nx-1) * divisor) < 2/3 (0.496 at 128^3 / R=64)
-    static const bool force_direct = getenv("VTACO_DECODE_DIRECT") != nullptr;       // A/B knob for tests and benches
-    if (a.brick && !force_direct && R >= 4 && lattice_nx <= 512 && !c_direct) {
-        const double s_vox = (double)(R - 1) * (double)lattice_box / ((double)(lattice_nx - 1) * (double)a.divisor);
-        const size_t lds_st = ((size_t)VT_BLOB_FLOATS + 4u * (size_t)lattice_nx + (size_t)(ST_THREADS / 64) * ST_WAVE_FLOATS) * sizeof(float);
-        const size_t lds_st2 = ((size_t)VT_BLOB_FLOATS + 4u * (size_t)lattice_nx) * sizeof(float) + (size_t)(ST2_THREADS / 64) * ST2_WAVE_BYTES + VT_TAIL_LDS_BYTES;
-        static const bool no_pair = getenv("VTACO_DECODE_NO_PAIR") != nullptr;    // A/B knob
+    const int form = pts ? VT_LATTICE_LINEAR
+                         : decode_lattice_form(P, R, lattice_nx, lattice_box, lattice_first, N, padding, out2 != nullptr, c_direct != nullptr, save != nullptr);
+    a.brick = form != VT_LATTICE_LINEAR;
+    if (a.brick) {                                         // the LDS-staged gathers; what is left below is the direct kernel
 #ifdef VT_DECODE_F16_TU
         if constexpr (P == 2) {
-            // slot-pipelined double-brick kernel (decode_st3.h); VTACO_DECODE_ST3=0 falls back to the compiler-scheduled one,
-            // VTACO_DECODE_ST3_SPLIT=0 selects the 4-instruction relu/split (mix-to-half) instead of the 5-instruction one
-            static const bool no_st3 = getenv("VTACO_DECODE_ST3") != nullptr && atoi(getenv("VTACO_DECODE_ST3")) == 0;
+            // slot-pipelined double-brick kernel (decode_st3.h); VTACO_DECODE_ST3_SPLIT=0 selects the 4-instruction relu/split
+            // (mix-to-half) instead of the 5-instruction one
             static const bool mix_half = getenv("VTACO_DECODE_ST3_SPLIT") != nullptr && atoi(getenv("VTACO_DECODE_ST3_SPLIT")) == 0;
-            if (!no_st3 && !no_pair && !out2 && st3_covers(lattice_nx, R, s_vox)) return st3_launch(a, mix_half ? 0 : 1, stream);
+            if (form == VT_LATTICE_STAGED3) return st3_launch(a, mix_half ? 0 : 1, stream);
         }
 #endif
-        if (!no_pair && !out2 && (lattice_nx & 7) == 0 && R >= 6 && s_vox > 0.0 && s_vox < 0.55 &&
-            lds_st2 <= 160u * 1024u) {
+        if (form == VT_LATTICE_STAGED2) {
+            const size_t lds_st2 = ((size_t)VT_BLOB_FLOATS + 4u * (size_t)lattice_nx) * sizeof(float) + (size_t)(ST2_THREADS / 64) * ST2_WAVE_BYTES + VT_TAIL_LDS_BYTES;
             const int64_t nt = (int64_t)a.total / 64;
             int64_t blocks = (nt + ST2_THREADS / 64 - 1) / (ST2_THREADS / 64);
             if (blocks > vt_num_cus()) blocks = vt_num_cus();
@@ -1238,7 +1273,8 @@ static int decode_launch(const float *grid_cl, const float *c_direct, int B, int
             hipLaunchKernelGGL(decode_fwd_staged2_kernel<P>, dim3((unsigned)blocks), dim3(ST2_THREADS), lds_st2, (hipStream_t)stream, a);
             return vt_check(hipGetLastError(), "vt_decode_fwd");
         }
-        if (s_vox > 0.0 && s_vox < 0.66 && lds_st <= 160u * 1024u) {
+        if (form == VT_LATTICE_STAGED) {
+            const size_t lds_st = ((size_t)VT_BLOB_FLOATS + 4u * (size_t)lattice_nx + (size_t)(ST_THREADS / 64) * ST_WAVE_FLOATS) * sizeof(float);
             const int64_t nt = (int64_t)a.total / 32;
             int64_t blocks = (nt + ST_THREADS / 64 - 1) / (ST_THREADS / 64);
             if (blocks > vt_num_cus()) blocks = vt_num_cus();
@@ -1284,10 +1320,19 @@ extern "C" {
 
 #ifdef VT_DECODE_F16_TU
 int vt_decode_f16f8_covers(int R, int C, int lattice_nx, float lattice_box, int64_t lattice_first, int64_t N, double padding) {
-    if (C != 32 || lattice_nx < 8 || N <= 0) return 0;
-    const int64_t pair = 2ll * lattice_nx * lattice_nx;
-    if (lattice_first % pair != 0 || N % pair != 0) return 0;
-    return st3_covers(lattice_nx, R, lattice_step_voxels(R, lattice_nx, lattice_box, padding)) ? 1 : 0;
+    if (C != 32) return 0;
+    return decode_lattice_form(VT_PRECISION_F16F8, R, lattice_nx, lattice_box, lattice_first, N, padding, false, false, false) == VT_LATTICE_STAGED3 ? 1 : 0;
+}
+
+int vt_decode_lattice_form(int R, int C, int lattice_nx, float lattice_box, int64_t lattice_first, int64_t N, double padding,
+                           int precision, int want_contact, int have_c_direct) {
+    if (precision < VT_PRECISION_F32 || precision > VT_PRECISION_F16F8) return VT_ERR_INVALID;
+    if (R < 2 || N < 0 || lattice_nx < 2) return VT_ERR_INVALID;
+    if (C != 32) return VT_ERR_UNSUPPORTED;
+    const int64_t all = (int64_t)lattice_nx * lattice_nx * lattice_nx;
+    if (lattice_first < 0 || lattice_first + N > all) return VT_ERR_INVALID;
+    if (precision == VT_PRECISION_F16F8 && (want_contact || have_c_direct)) return VT_ERR_UNSUPPORTED;
+    return decode_lattice_form(precision, R, lattice_nx, lattice_box, lattice_first, N, padding, want_contact != 0, have_c_direct != 0, false);
 }
 
 int vt_decode_fwd_f16f8(const float *grid_cl, int B, int R, int C, int64_t N, int lattice_nx, float lattice_box, int64_t lattice_first,
@@ -1299,7 +1344,7 @@ int vt_decode_fwd_f16f8(const float *grid_cl, int B, int R, int C, int64_t N, in
     if (B <= 0 || N < 0) return vt_fail(VT_ERR_INVALID, "vt_decode_fwd_f16f8: bad size");
     if (N == 0) return 0;
     if ((int64_t)B * N >= (int64_t)1 << 31) return vt_fail(VT_ERR_UNSUPPORTED, "vt_decode_fwd_f16f8: B*N must be < 2^31");
-    if (!vt_decode_f16f8_covers(R, C, lattice_nx, lattice_box, lattice_first, N, padding))
+    if (C != 32 || decode_lattice_form(VT_PRECISION_F16F8, R, lattice_nx, lattice_box, lattice_first, N, padding, false, false, false) != VT_LATTICE_STAGED3)
         return vt_fail(VT_ERR_UNSUPPORTED, "vt_decode_fwd_f16f8: covers lattice slabs of whole x-plane pairs with nx % 8 == 0 and < 0.55 voxels per "
                                            "step (vt_decode_f16f8_covers); use vt_decode_fwd_f16x3 otherwise");
     DecodeArgs a;

@@ -29,6 +29,24 @@ def f16f8_covers(grid, lattice, padding=0.1):
     return bool(_lib.load().vt_decode_f16f8_covers(D, C, int(nx), float(box), int(first), int(count), float(padding)))
 
 
+LATTICE_FORMS = ("linear", "brick", "staged", "staged2", "staged3")   # VT_LATTICE_*: the kernel forms of a lattice decode
+
+
+def decode_lattice_form(R, lattice, padding=0.1, precision="f32", want_contact=False, c_direct=False, C=32):
+    """The kernel form a lattice decode of this shape takes (vt_decode_lattice_form: the launchers' own dispatch rule, asked
+    without launching anything): one of LATTICE_FORMS for a grid of side ``R`` with ``C`` channels, ``lattice=(nx, box, first,
+    count)`` and a precision of PRECISIONS; ``c_direct``: the features are given (decode_mlp_fwd).  Raises VtError where the
+    launcher would refuse the call."""
+    if precision not in PRECISIONS:
+        raise VtError(f"precision must be one of {PRECISIONS} (got {precision!r})")
+    nx, box, first, count = lattice
+    rc = _lib.load().vt_decode_lattice_form(int(R), int(C), int(nx), float(box), int(first), int(count), float(padding),
+                                            PRECISIONS.index(precision), int(bool(want_contact)), int(bool(c_direct)))
+    if rc < 0:
+        raise VtError(f"decode_lattice_form: no {precision!r} lattice decode of R={R}, C={C}, lattice={tuple(lattice)} (code {rc})")
+    return LATTICE_FORMS[rc]
+
+
 def pack_decoder(fc_p_w, fc_p_b, fc_c, blocks, fc_out, fc_out2=None, out=None, transposed=False, precision="f32"):
     """Repack decoder parameters into the MFMA-fragment blob (vt_decoder_pack; with
     ``precision="bf16x3"`` / ``"f16x3"`` the split blob of vt_decoder_pack_bf16x3 / _f16x3), or with
