@@ -105,6 +105,25 @@ def test_tree_arrays_equal_the_definition_byte_for_byte(clouds):
     log("EQUAL BITS point_tree build 1025: pyramids, offsets, lists, boxes, points")
 
 
+def test_a_minimum_of_minus_zero_is_stored_as_plus_zero(clouds):
+    """The point tree adds + 0.0 to the frame's minimum corner (the face tree does not): the sign bit of a zero is part of the bytes."""
+    from vtaco_amd import ops
+    dst = clouds[("dst", 64)].copy()
+    dst[:, 1] -= dst[:, 1].min()
+    dst[dst[:, 1] == 0, 1] = -0.0                                   # y is -0.0 or positive: no +0.0 for the minimum to tie with
+    assert np.signbit(dst[:, 1].min()) and (dst[:, 1] == 0).sum() == 1
+    tree, ref = ops.icp.point_tree_build(dev(dst), 2), P.build(dst, 2)
+    assert not np.signbit(ref["lo"][1]) and ref["lo"][1] == 0.0
+    assert tree.frame().cpu().numpy().tobytes() == np.append(ref["lo"], ref["side"]).tobytes()
+    assert tree.counts == ref["counts"]
+    for l in range(tree.depth + 1):
+        assert np.array_equal(tree.pyramid(l).cpu().numpy(), ref["pyramids"][l]), l
+        assert same_bits(tree.boxes(l).cpu().numpy(), ref["boxes"][l]), l
+    assert np.array_equal(tree.list_offsets().cpu().numpy(), ref["offsets"])
+    assert np.array_equal(tree.lists().cpu().numpy(), ref["lists"])
+    assert same_bits(tree.points().cpu().numpy(), ref["points"])
+
+
 # ---- degenerate sets and awkward queries ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", sorted(P.special_cases()))
 def test_special_cases(monkeypatch, name):
@@ -134,21 +153,26 @@ def test_float32_inputs_and_a_batch_of_three(clouds):
     w_d2, w_idx = R.kernel_order.nn(s32.astype(np.float64), d32.astype(np.float64))
     assert d2.dtype == torch.float64 and np.array_equal(idx.cpu().numpy(), w_idx) and same_bits(d2.cpu().numpy(), w_d2)
     src, dst, T = P.batch_of_three()
-    tree = ops.icp.point_tree_build(dev(dst))
-    d2, idx, stats = ops.icp.point_tree_query(tree, dev(src), T=dev(T), stats=True)
-    b_d2, b_idx = ops.icp.nn_points(dev(src), dev(dst), T=dev(T))
-    assert same_bits(d2.cpu().numpy(), b_d2.cpu().numpy()) and np.array_equal(idx.cpu().numpy(), b_idx.cpu().numpy())
-    assert len({tuple(c) for c in tree.counts}) == 3                  # different occupancies share one layout
-    for b in range(3):
-        ref = P.build(dst[b])
-        w_d2, w_idx, w_stats = P.query(ref, src[b], T[b])
-        assert same_bits(d2[b].cpu().numpy(), w_d2) and np.array_equal(idx[b].cpu().numpy(), w_idx), b
-        assert np.array_equal(stats[b].cpu().numpy(), w_stats), b
-        assert tree.counts[b] == ref["counts"]
-        for l in range(tree.depth + 1):
-            assert same_bits(tree.boxes(l, b).cpu().numpy(), ref["boxes"][l]), (b, l)
-        assert np.array_equal(tree.lists(b).cpu().numpy(), ref["lists"]) and same_bits(tree.points(b).cpu().numpy(), ref["points"])
-        assert np.array_equal(tree.list_offsets(b).cpu().numpy(), ref["offsets"])
+    flat = dst.copy()
+    flat[1, :, 2] = flat[1, 0, 2]                                     # depth 1: problem 0 fills 8 leaves, problem 1 (a plane) 4, problem 2 3
+    for depth, dst in ((None, dst), (1, flat)):
+        tree = ops.icp.point_tree_build(dev(dst), depth)
+        assert tree.depth == (3 if depth is None else depth)
+        d2, idx, stats = ops.icp.point_tree_query(tree, dev(src), T=dev(T), stats=True)
+        b_d2, b_idx = ops.icp.nn_points(dev(src), dev(dst), T=dev(T))
+        assert same_bits(d2.cpu().numpy(), b_d2.cpu().numpy()) and np.array_equal(idx.cpu().numpy(), b_idx.cpu().numpy())
+        assert len({tuple(c) for c in tree.counts}) == 3              # different occupancies share one layout
+        for b in range(3):
+            ref = P.build(dst[b], depth)
+            w_d2, w_idx, w_stats = P.query(ref, src[b], T[b])
+            assert same_bits(d2[b].cpu().numpy(), w_d2) and np.array_equal(idx[b].cpu().numpy(), w_idx), (depth, b)
+            assert np.array_equal(stats[b].cpu().numpy(), w_stats), (depth, b)
+            assert tree.counts[b] == ref["counts"]
+            for l in range(tree.depth + 1):
+                assert np.array_equal(tree.pyramid(l, b).cpu().numpy(), ref["pyramids"][l]), (depth, b, l)
+                assert same_bits(tree.boxes(l, b).cpu().numpy(), ref["boxes"][l]), (depth, b, l)
+            assert np.array_equal(tree.lists(b).cpu().numpy(), ref["lists"]) and same_bits(tree.points(b).cpu().numpy(), ref["points"])
+            assert np.array_equal(tree.list_offsets(b).cpu().numpy(), ref["offsets"])
     log("EQUAL BITS point_tree batch of 3: d2, idx, stats, boxes, lists, points per problem")
 
 

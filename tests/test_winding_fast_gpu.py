@@ -95,6 +95,19 @@ def test_tree_stats_and_w_against_the_restatement(F, N, depth):
                f"(atan2 assumed {ATAN2_ULP:g} ulp)")
 
 
+def test_a_minimum_of_minus_zero_stays_minus_zero_in_the_frame():
+    """The face tree stores the vertices' minimum as it is (the point tree stores a zero as +0.0): ``np.array_equal`` cannot see that."""
+    from vtaco_amd import ops
+    v, f = C.CUBE_V.copy(), C.CUBE_F
+    v[:, 0] += np.float32(0.25)
+    v[v[:, 0] == 0, 0] = np.float32(-0.0)                           # x is -0.0 or 0.5: no +0.0 for the minimum to tie with
+    ref = W.build(v, f, 2)
+    assert np.signbit(ref.lo[0]) and ref.lo[0] == 0.0
+    tree = ops.winding.build(_t(v), _t(f), 2)
+    assert tree.frame.cpu().numpy().tobytes() == np.append(ref.lo, ref.side).astype(np.float64).tobytes()
+    assert_tree_equals(tree, ref)
+
+
 def test_default_depth_and_fast():
     from vtaco_amd import ops
     assert [ops.winding.default_depth(F) for F in (0, 1, 64, 65, 512, 513, 4096, 4097, 976125, 10 ** 8)] == \

@@ -3,7 +3,8 @@
 // tests/closest_point_tree_ref.py: this file's operations in this file's order.
 //   inputs    a built winding tree (pyramids, list offsets, lists, the per-level counts the caller read back) and the mesh it was built on
 //   boxes     one axis-aligned box per occupied cell of every level, lo[3], hi[3] in float64: a leaf's is the min / max over the exactly
-//             converted corners of the faces in its list, an inner cell's the min / max over its occupied children.  A face with an index
+//             converted corners of the faces in its list, an inner cell's the min / max over its occupied children (octree_common.h's
+//             ot_inner_box_kernel).  A face with an index
 //             outside [0, V) is in no box (status bit 1, as closest_point.hip reports it); a cell of such faces only has lo = +inf, hi = -inf
 //   records   closest_point_face.h's 14 doubles per face, in list order: a leaf's faces are contiguous; slot t holds face lists[t]
 //   query     one lane per query, float64, winding_fast.hip's walk without a stack: the state is (level, cell), "next" is cell + 1 climbing
@@ -13,7 +14,7 @@
 //   delta     2^-40 S^2, S = ((m_x + m_y) + m_z) + 4 side, m_a = max(|p_a - lo_a|, |p_a - (lo_a + side)|) over the tree's frame: S bounds
 //             |p - a| + |ab| + |ac| of every face, and the computed d2 undercuts the true squared distance to a cell's box by less than
 //             40 u S^2, u = 2^-53 (DESIGN.md derives the count); 2^-40 = 8192 u.  A NaN coordinate makes delta NaN: nothing is skipped
-//   seed      before the walk, the leaf reached by descending towards the query's own cell (winding_fast.hip's binning, clamped into the
+//   seed      before the walk, the leaf reached by descending towards the query's own cell (octree_common.h's binning, clamped into the
 //             frame; where the wanted child is empty, the occupied child whose number is nearest, the lower of two) is evaluated, so the
 //             walk starts with a finite best; the walk passes over that leaf
 //   order     the children of a cell are visited as k ^ o, o the octant of the query about the cell's centre
@@ -28,30 +29,26 @@
 
 #include "closest_point_face.h"
 #include "mesh_common.h"
+#include "octree_common.h"
 #include "vt_common.h"
 #include "vtaco_hip.h"
 
 namespace {
 
-constexpr int CT_LEVELS = VT_WN_MAX_DEPTH + 1;
-constexpr int CT_BOX = 6;                       // doubles per box (48 bytes: 16-byte aligned rows): lo[3], hi[3]
+constexpr int CT_BOX = OT_BOX;                  // doubles per box (48 bytes: 16-byte aligned rows): lo[3], hi[3]
 constexpr size_t CT_HEAD = 256;                 // bytes in front of the boxes; the status word is the first
 constexpr double CT_SLACK = 0x1p-40;
 
-int64_t ct_cells_of(int l) { return (int64_t)1 << (3 * l); }
-int64_t ct_pyr_off(int l) { return (ct_cells_of(l) - 1) / 7; }
-
-struct CtBase { int v[CT_LEVELS + 1]; };
-struct CtSide { size_t box, rec, bytes; CtBase base; };
+struct CtSide { size_t box, rec, bytes; OtBase base; };
 
 // the side buffer of a tree with these counts (state_host: vt_winding_tree_count's words, validated by vt_winding_tree_layout first)
 void ct_side(int64_t F, int L, const int32_t *state, CtSide &s) {
     int64_t total = 0;
-    for (int l = 0; l < CT_LEVELS; ++l) {
+    for (int l = 0; l < OT_LEVELS; ++l) {
         s.base.v[l] = (int)total;
         if (l <= L) total += state[1 + l];
     }
-    s.base.v[CT_LEVELS] = (int)total;
+    s.base.v[OT_LEVELS] = (int)total;
     s.box = CT_HEAD;
     s.rec = s.box + up256((size_t)total * CT_BOX * sizeof(double));
     s.bytes = s.rec + up256((size_t)F * CP_REC * sizeof(double));
@@ -106,28 +103,6 @@ ct_leaf_box_kernel(const int32_t *pyr_leaf, int64_t cells, const int32_t *loff, 
     for (int a = 0; a < 3; ++a) { b[a] = lo[a]; b[3 + a] = hi[a]; }
 }
 
-__global__ void __launch_bounds__(MT_THREADS)
-ct_inner_box_kernel(const int32_t *pyr, const int32_t *pyr_child, int64_t cells, const double *box_child, double *box_level) {
-    const int64_t m = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
-    if (m >= cells) return;
-    const int rk = pyr[m];
-    if (rk < 0) return;
-    double lo[3] = {__builtin_inf(), __builtin_inf(), __builtin_inf()}, hi[3] = {-__builtin_inf(), -__builtin_inf(), -__builtin_inf()};
-    for (int k = 0; k < 8; ++k) {
-        const int ck = pyr_child[8 * m + k];
-        if (ck < 0) continue;
-        const double *c = box_child + (size_t)ck * CT_BOX;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = c[a] < lo[a] ? c[a] : lo[a];
-            hi[a] = c[3 + a] > hi[a] ? c[3 + a] : hi[a];
-        }
-    }
-    double *b = box_level + (size_t)rk * CT_BOX;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { b[a] = lo[a]; b[3 + a] = hi[a]; }
-}
-
 // ---- query ---------------------------------------------------------------------------------------------------------------------------
 struct CtBest { double d2; int face, slot; };
 
@@ -148,22 +123,9 @@ __device__ inline int ct_leaf(const int32_t *loff, const int32_t *list, const do
     return e - o;
 }
 
-__device__ inline unsigned ct_spread(unsigned x) {           // bit k -> bit 3k, 7 bits
-    unsigned r = 0;
-#pragma unroll
-    for (int k = 0; k < VT_WN_MAX_DEPTH; ++k) r |= ((x >> k) & 1u) << (3 * k);
-    return r;
-}
-__device__ inline unsigned ct_gather(unsigned m) {           // bit 3k -> bit k, 7 bits
-    unsigned r = 0;
-#pragma unroll
-    for (int k = 0; k < VT_WN_MAX_DEPTH; ++k) r |= ((m >> (3 * k)) & 1u) << k;
-    return r;
-}
-
 template <bool SEED, bool ORDER>
 __global__ void __launch_bounds__(MT_THREADS)
-ct_query_kernel(const char *tree, size_t pyr_at, size_t loff_at, size_t list_at, const char *side, size_t box_at, size_t rec_at, CtBase base, int L,
+ct_query_kernel(const char *tree, size_t pyr_at, size_t loff_at, size_t list_at, const char *side, size_t box_at, size_t rec_at, OtBase base, int L,
                 const float *pts, int64_t N, double *d2, int32_t *face, double *closest, int32_t *stats) {
     const int64_t n = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
     if (n >= N) return;
@@ -194,7 +156,7 @@ ct_query_kernel(const char *tree, size_t pyr_at, size_t loff_at, size_t list_at,
             double g = floor((p[a] - flo[a]) / fside * (double)cells);
             g = g > 0.0 ? g : 0.0;                                 // (a NaN becomes 0)
             g = g < (double)(cells - 1) ? g : (double)(cells - 1);
-            code |= ct_spread((unsigned)(int)g) << a;
+            code |= ot_spread((unsigned)(int)g) << a;
         }
         unsigned c = 0, at = 0;
         bool found = true;
@@ -243,7 +205,7 @@ ct_query_kernel(const char *tree, size_t pyr_at, size_t loff_at, size_t list_at,
                 const double h = fside * (1.0 / (double)(1 << level));
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
-                    const double centre = flo[a] + ((double)ct_gather(actual >> a) + 0.5) * h;
+                    const double centre = flo[a] + ((double)ot_gather(actual >> a) + 0.5) * h;
                     o |= p[a] >= centre ? 1u << a : 0u;
                 }
             }
@@ -301,13 +263,13 @@ int vt_closest_tree_build(const float *verts, int64_t V, const int32_t *faces, i
     if (int rc = vt_fill32(sd, 0u, CT_HEAD, st)) return rc;
     hipLaunchKernelGGL(ct_record_kernel, dim3(blocks_of(F, MT_THREADS)), dim3(MT_THREADS), 0, st, verts, (int)V, faces, list, (int)F, recs,
                        reinterpret_cast<int32_t *>(sd));
-    const int64_t leaf = ct_cells_of(depth);
-    hipLaunchKernelGGL(ct_leaf_box_kernel, dim3(blocks_of(leaf, MT_THREADS)), dim3(MT_THREADS), 0, st, pyr + ct_pyr_off(depth), leaf, loff, list, verts,
+    const int64_t leaf = cells_of(depth);
+    hipLaunchKernelGGL(ct_leaf_box_kernel, dim3(blocks_of(leaf, MT_THREADS)), dim3(MT_THREADS), 0, st, pyr + pyr_off(depth), leaf, loff, list, verts,
                        (int)V, faces, (int)F, boxes + (size_t)s.base.v[depth] * CT_BOX);
     for (int l = depth - 1; l >= 0; --l)
-        hipLaunchKernelGGL(ct_inner_box_kernel, dim3(blocks_of(ct_cells_of(l), MT_THREADS)), dim3(MT_THREADS), 0, st, pyr + ct_pyr_off(l),
-                           pyr + ct_pyr_off(l + 1), ct_cells_of(l), (const double *)(boxes + (size_t)s.base.v[l + 1] * CT_BOX),
-                           boxes + (size_t)s.base.v[l] * CT_BOX);
+        hipLaunchKernelGGL(ot_inner_box_kernel, dim3(blocks_of(cells_of(l), MT_THREADS)), dim3(MT_THREADS), 0, st, tr, (size_t)0,
+                           off[0] + (size_t)pyr_off(l) * 4, off[0] + (size_t)pyr_off(l + 1) * 4, cells_of(l), sd, (size_t)0,
+                           s.box + (size_t)s.base.v[l + 1] * CT_BOX * sizeof(double), s.box + (size_t)s.base.v[l] * CT_BOX * sizeof(double));
     return vt_check(hipGetLastError(), "vt_closest_tree_build");
 }
 

@@ -40,6 +40,7 @@
 #include <string.h>
 
 #include "mesh_common.h"
+#include "octree_common.h"
 #include "ray_face.h"
 #include "vt_common.h"
 #include "vtaco_hip.h"
@@ -51,7 +52,6 @@ constexpr int RM_MIN_CHUNKS = 2;                // chunks per slab at least: eve
 constexpr int RM_TARGET_BLOCKS = 2048;          // workgroups wanted per launch: 8 per CU
 constexpr size_t RM_HEAD = 256;                 // bytes in front of the workspace; the call's status word is the first
 constexpr int RM_BAD_INDEX = 1;                 // status bit (closest_point_face.h's CP_BAD_INDEX)
-constexpr int RT_LEVELS = VT_WN_MAX_DEPTH + 1;
 constexpr int RT_BOX = 6;                       // closest_point_tree.hip's side buffer: doubles per box, doubles per face record, the kind's slot
 constexpr int RT_CP_REC = 14;
 constexpr int RT_CP_KIND = 12;
@@ -174,7 +174,6 @@ rm_finish_kernel(int F, const double *origins, int64_t per_origin, const double 
 }
 
 // ---- the tree walk -------------------------------------------------------------------------------------------------------------------------
-struct RtBase { int v[RT_LEVELS + 1]; };
 struct RtBest { double s; int face, slot; };
 
 __device__ inline void rt_corners(const float *tri, int t, double p[9]) {
@@ -201,7 +200,7 @@ __device__ inline int rt_leaf(const int32_t *loff, const int32_t *list, const fl
 template <bool ORDER>
 __global__ void __launch_bounds__(MT_THREADS)
 rt_query_kernel(const char *tree, size_t pyr_at, size_t loff_at, size_t list_at, size_t tri_at, const char *side, size_t box_at, size_t rec_at,
-                RtBase base, int L, const double *origins, int64_t per_origin, const double *dirs, int64_t N, double t_min, double t_max,
+                OtBase base, int L, const double *origins, int64_t per_origin, const double *dirs, int64_t N, double t_min, double t_max,
                 double *s_out, int32_t *face, double *bary, int32_t *stats) {
     const int64_t n = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
     if (n >= N) return;
@@ -362,9 +361,9 @@ int vt_ray_tree_query(const void *tree, size_t tree_bytes, const void *side, siz
     if (int rc = vt_closest_tree_layout(F, depth, state_host, soff)) return rc;
     if (tree_bytes < off[5] || side_bytes < soff[2]) return vt_fail(VT_ERR_WORKSPACE, "vt_ray_tree_query: tree or side buffer too small");
     if (N == 0) return 0;
-    RtBase base;
+    OtBase base;
     int64_t total = 0;
-    for (int l = 0; l <= RT_LEVELS; ++l) {
+    for (int l = 0; l <= OT_LEVELS; ++l) {
         base.v[l] = (int)total;
         if (l <= depth) total += state_host[1 + l];
     }

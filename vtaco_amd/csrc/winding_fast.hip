@@ -5,11 +5,8 @@
 // in numpy by tests/winding_fast_ref.py: this file's operations in this file's order.
 //   inputs    verts [V,3] f32, faces [F,3] i32 (indices clamped to [0, V) as winding_kernel clamps them), pts [N,3] f32; every number
 //             below is float64 on the exactly converted inputs, every product and sum a separate rounding (-ffp-contract=off)
-//   frame     lo = the vertices' minimum corner, side = their largest extent (1 when 0), n = 2^depth cells per axis, 1 <= depth <= 7
-//   binning   a face lives in the leaf of its centroid ((a + b) + c) / 3; cells are numbered in Morton order (bit 3k of a cell number
-//             is bit k of ix, 3k+1 of iy, 3k+2 of iz): the children of cell m at level l are 8m .. 8m+7 at level l + 1
-//   pyramid   per level a dense int32 [8^l]: the rank of an occupied cell among its level's occupied cells, or -1
-//   lists     count, scan, fill through an integer cursor, then every face is placed at its rank inside its leaf: ascending face index
+//   tree      octree_common.h's octree with WfSource below: the frame spans the vertices, a face lives in the leaf of its centroid
+//             ((a + b) + c) / 3 and carries its corners (9 f32) in list order; pyramids, lists ascending by face index
 //   record    36 doubles per occupied cell: p, r, N0, M1[j][i], M2[jk][i] (jk = 00 01 02 11 12 22), total area, face count.  A leaf is
 //             summed by one thread over its list, an inner cell by one thread over its children in Morton order: no float atomic, one
 //             order, the records are equal from run to run and equal to the restatement's bit for bit
@@ -17,256 +14,58 @@
 //             cell % 8 == 0, "descend" is (level + 1, 8 cell).  A cell with |q - p|^2 > accuracy^2 r^2 adds its expansion, a leaf that is
 //             not accepted the Van Oosterom-Strackee solid angles of its faces in list order; w = (far + near) / 4 pi
 // No launch function allocates, copies to the host or waits: the one host read of a build (the occupied cells per level and the status
-// word, the first 64 bytes of vt_winding_tree_count's workspace) is the caller's, between the two calls.
+// word, the first 64 bytes of vt_winding_tree_count's workspace: octree_common.h's state words) is the caller's, between the two calls.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "mesh_common.h"
+#include "octree_common.h"
 #include "vt_common.h"
 #include "vtaco_hip.h"
 
 namespace {
 
 constexpr int WF_REC = 36;                      // doubles per cell record (288 bytes: 16-byte aligned rows)
-constexpr int WF_LEVELS = VT_WN_MAX_DEPTH + 1;
-constexpr int WF_BAD_VERTEX = 1;                // status bit: a vertex coordinate that is not finite
-constexpr size_t WF_HEAD = 256;                 // tree header: lo[3], side (doubles at 0), rec_base[9] (int32 at byte 64)
-// workspace words (int32) of the count call: 0 status, 1..8 occupied cells of level 0..7, 10 the list scan's total;
-// bytes 64..111 the bounding box as ordered keys, bytes 128..159 lo[3] and side
-constexpr int WF_W_COUNT = 1;
-constexpr int WF_W_TOTAL = 10;
-
-int64_t cells_of(int l) { return (int64_t)1 << (3 * l); }
-int64_t pyr_off(int l) { return (cells_of(l) - 1) / 7; }     // cells of the levels above l
-
-struct WfWork { size_t codes, cnt, doff, pyr, tmp, bsum, bytes; };
-WfWork wf_work(int64_t F, int L) {
-    WfWork w;
-    const size_t leaf = (size_t)cells_of(L);
-    w.codes = MT_STATUS_BYTES;
-    w.cnt = w.codes + up256((size_t)F * 4);
-    w.doff = w.cnt + up256(leaf * 4);
-    w.pyr = w.doff + up256(leaf * 4);
-    w.tmp = w.pyr + up256((size_t)pyr_off(L + 1) * 4);
-    w.bsum = w.tmp + up256((size_t)F * 4);
-    w.bytes = w.bsum + scan_bytes((int64_t)leaf);
-    return w;
-}
-
-struct WfTree { size_t pyr, rec, loff, list, tri, bytes; int rec_base[WF_LEVELS + 1]; };
-bool wf_tree(int64_t F, int L, const int32_t *state, WfTree &t) {
-    int64_t total = 0;
-    for (int l = 0; l < WF_LEVELS; ++l) {
-        t.rec_base[l] = (int)total;
-        if (l <= L) {
-            const int64_t c = state[WF_W_COUNT + l];
-            if (c < 0 || c > cells_of(l) || c > F) return false;
-            total += c;
-        }
-    }
-    t.rec_base[WF_LEVELS] = (int)total;
-    if (total > 0x7fffffff) return false;
-    const int64_t leaves = state[WF_W_COUNT + L];
-    t.pyr = WF_HEAD;
-    t.rec = t.pyr + up256((size_t)pyr_off(L + 1) * 4);
-    t.loff = t.rec + up256((size_t)total * WF_REC * sizeof(double));
-    t.list = t.loff + up256((size_t)(leaves + 1) * 4);
-    t.tri = t.list + up256((size_t)F * 4);
-    t.bytes = t.tri + up256((size_t)F * 9 * sizeof(float));
-    return true;
-}
-
-// ---- count: frame, codes, pyramids, list offsets -----------------------------------------------------------------------------------
-__global__ void wf_init_kernel(int32_t *state) {
-    if (threadIdx.x < 64) state[threadIdx.x] = 0;
-    __syncthreads();
-    u64 *keys = reinterpret_cast<u64 *>(state + 16);
-    if (threadIdx.x < 3) keys[threadIdx.x] = ~0ull;          // minima
-}
-
-__global__ void __launch_bounds__(MT_THREADS) wf_bbox_kernel(const float *verts, int64_t V, int32_t *state) {
-    __shared__ float lds[6][MT_THREADS];
-    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    bool bad = false;
-    for (int64_t v = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x; v < V; v += (int64_t)gridDim.x * MT_THREADS) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float x = verts[3 * v + a];
-            if (!(fabsf(x) < __builtin_inff())) { bad = true; continue; }
-            lo[a] = fminf(lo[a], x); hi[a] = fmaxf(hi[a], x);
-        }
-    }
-    if (bad) atomicOr(state, WF_BAD_VERTEX);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { lds[a][threadIdx.x] = lo[a]; lds[3 + a][threadIdx.x] = hi[a]; }
-    __syncthreads();
-    for (int d = MT_THREADS / 2; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                lds[a][threadIdx.x] = fminf(lds[a][threadIdx.x], lds[a][threadIdx.x + d]);
-                lds[3 + a][threadIdx.x] = fmaxf(lds[3 + a][threadIdx.x], lds[3 + a][threadIdx.x + d]);
-            }
-        }
-        __syncthreads();
-    }
-    u64 *keys = reinterpret_cast<u64 *>(state + 16);
-    if (threadIdx.x < 3) atomicMin(keys + threadIdx.x, key_of((double)lds[threadIdx.x][0]));
-    else if (threadIdx.x < 6) atomicMax(keys + threadIdx.x, key_of((double)lds[threadIdx.x][0]));
-}
-
-__global__ void wf_frame_kernel(int32_t *state) {
-    const u64 *keys = reinterpret_cast<const u64 *>(state + 16);
-    double *frame = reinterpret_cast<double *>(state + 32);
-    double ext = 0.0;
-    for (int a = 0; a < 3; ++a) {
-        const double lo = value_of(keys[a]), hi = value_of(keys[3 + a]);
-        frame[a] = lo;
-        const double e = hi - lo;
-        ext = e > ext ? e : ext;
-    }
-    frame[3] = ext > 0.0 ? ext : 1.0;
-}
 
 __device__ inline int wf_clamp(int v, int V) { return v < 0 ? 0 : (v >= V ? V - 1 : v); }
 
-__device__ inline void wf_corners(const float *verts, int V, const int32_t *faces, int64_t f, double p[3][3]) {
+// octree_common.h's source of a mesh: the frame spans the vertices, a face is binned by its centroid and carries its corners
+struct WfSource {
+    const float *verts;
+    const int32_t *faces;
+    int V, F;
+    static constexpr size_t PAYLOAD = 9 * sizeof(float);
+    __host__ __device__ int coords() const { return V; }
+    __host__ __device__ int items() const { return F; }
+    __device__ double coord(int, int64_t v, int a) const { return (double)verts[3 * v + a]; }
+    __device__ double frame_lo(double x) const { return x; }
+    __device__ void point(int, int64_t f, double c[3]) const {
+        double p[3][3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int vi = wf_clamp(faces[3 * f + k], V);
+        for (int k = 0; k < 3; ++k) {
+            const int vi = wf_clamp(faces[3 * f + k], V);
 #pragma unroll
-        for (int a = 0; a < 3; ++a) p[k][a] = (double)verts[3 * (size_t)vi + a];
+            for (int a = 0; a < 3; ++a) p[k][a] = (double)verts[3 * (size_t)vi + a];
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) c[a] = ((p[0][a] + p[1][a]) + p[2][a]) / 3.0;
     }
-}
-
-__device__ inline unsigned wf_spread(unsigned x) {          // bit k -> bit 3k, 7 bits
-    unsigned r = 0;
+    __device__ void payload(int, int64_t f, char *slot) const {
+        float *tri = reinterpret_cast<float *>(slot);
 #pragma unroll
-    for (int k = 0; k < VT_WN_MAX_DEPTH; ++k) r |= ((x >> k) & 1u) << (3 * k);
-    return r;
-}
-
-__global__ void __launch_bounds__(MT_THREADS)
-wf_code_kernel(const float *verts, int V, const int32_t *faces, int F, int L, const int32_t *state, int32_t *codes, int32_t *cnt) {
-    const int64_t f = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
-    if (f >= F) return;
-    const double *frame = reinterpret_cast<const double *>(state + 32);
-    double p[3][3];
-    wf_corners(verts, V, faces, f, p);
-    const int n = 1 << L;
-    unsigned code = 0;
+        for (int k = 0; k < 3; ++k) {
+            const int vi = wf_clamp(faces[3 * f + k], V);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double c = ((p[0][a] + p[1][a]) + p[2][a]) / 3.0;
-        double g = floor((c - frame[a]) / frame[3] * (double)n);
-        g = g > 0.0 ? g : 0.0;                                   // (a NaN becomes 0: such a mesh is refused at the host read)
-        g = g < (double)(n - 1) ? g : (double)(n - 1);
-        code |= wf_spread((unsigned)(int)g) << a;
-    }
-    codes[f] = (int32_t)code;
-    atomicAdd(cnt + code, 1);
-}
-
-struct WfLeafOcc {
-    const int32_t *cnt;
-    __device__ bool operator()(int64_t i) const { return cnt[i] > 0; }
-};
-struct WfInnerOcc {
-    const int32_t *child;                                        // the finished pyramid of the level below
-    __device__ bool operator()(int64_t i) const {
-        int all = -1;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) all &= child[8 * i + k];
-        return all >= 0;                                         // any child's rank is not negative
+            for (int a = 0; a < 3; ++a) tri[3 * k + a] = verts[3 * (size_t)vi + a];
+        }
     }
 };
 
-template <class P>
-__global__ void __launch_bounds__(MT_THREADS) wf_mark_empty_kernel(P pred, int64_t n, int32_t *pyr) {
-    const int64_t i = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
-    if (i < n && !pred(i)) pyr[i] = -1;
-}
+bool wf_tree(int64_t F, int L, const int32_t *state, OtTree &t) { return ot_tree(F, L, 1, state, WF_REC, WfSource::PAYLOAD, t); }
 
-// exclusive scan of int32 values, in the three phases of mesh_common.h's predicate scan
-__global__ void __launch_bounds__(MT_THREADS) wf_vscan_count_kernel(const int32_t *x, int64_t n, int32_t *bsum) {
-    __shared__ int lds[MT_THREADS];
-    const int64_t i0 = (int64_t)blockIdx.x * MT_CHUNK + (int64_t)threadIdx.x * MT_ITEMS;
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) s += i0 + k < n ? x[i0 + k] : 0;
-    const int incl = block_inclusive_scan(s, lds);
-    if (threadIdx.x == MT_THREADS - 1) bsum[blockIdx.x] = incl;
-}
-__global__ void __launch_bounds__(MT_THREADS) wf_vscan_write_kernel(const int32_t *x, int64_t n, const int32_t *bsum, int32_t *pos) {
-    __shared__ int lds[MT_THREADS];
-    const int64_t i0 = (int64_t)blockIdx.x * MT_CHUNK + (int64_t)threadIdx.x * MT_ITEMS;
-    int v[MT_ITEMS];
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) { v[k] = i0 + k < n ? x[i0 + k] : 0; s += v[k]; }
-    int at = bsum[blockIdx.x] + block_inclusive_scan(s, lds) - s;
-#pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) {
-        if (i0 + k < n) pos[i0 + k] = at;
-        at += v[k];
-    }
-}
-
-// ---- build: lists, corners in list order, records ---------------------------------------------------------------------------------
-struct WfBase { int v[WF_LEVELS + 1]; };
-
-__global__ void __launch_bounds__(MT_THREADS)
-wf_header_kernel(const int32_t *state, const int32_t *pyr_src, int64_t words, WfBase base, int L, int F, char *tree, size_t pyr_at) {
-    const int64_t i = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
-    if (i < words) reinterpret_cast<int32_t *>(tree + pyr_at)[i] = pyr_src[i];
-    if (i == 0) {
-        const double *frame = reinterpret_cast<const double *>(state + 32);
-        double *head = reinterpret_cast<double *>(tree);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) head[k] = frame[k];
-        int32_t *hb = reinterpret_cast<int32_t *>(tree + 64);
-#pragma unroll
-        for (int k = 0; k <= WF_LEVELS; ++k) hb[k] = base.v[k];
-        hb[16] = L; hb[17] = F;
-    }
-}
-
-__global__ void __launch_bounds__(MT_THREADS)
-wf_list_offsets_kernel(const int32_t *pyr_leaf, const int32_t *doff, int64_t cells, int leaves, int F, int32_t *loff) {
-    const int64_t m = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
-    if (m == 0) loff[leaves] = F;
-    if (m < cells && pyr_leaf[m] >= 0) loff[pyr_leaf[m]] = doff[m];
-}
-
-__global__ void __launch_bounds__(MT_THREADS) wf_fill_kernel(const int32_t *codes, int F, const int32_t *doff, int32_t *cursor, int32_t *tmp) {
-    const int64_t f = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
-    if (f >= F) return;
-    const int code = codes[f];
-    tmp[doff[code] + atomicAdd(cursor + code, 1)] = (int32_t)f;
-}
-
-// a face's place in its leaf is the number of that leaf's faces below it: the lists end ascending however the cursor filled them
-__global__ void __launch_bounds__(MT_THREADS)
-wf_rank_kernel(const float *verts, int V, const int32_t *faces, const int32_t *codes, int F, const int32_t *doff, const int32_t *cursor,
-               const int32_t *tmp, int32_t *list, float *tri) {
-    const int64_t f = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
-    if (f >= F) return;
-    const int code = codes[f];
-    const int o = doff[code], n = cursor[code];
-    int rank = 0;
-    for (int j = 0; j < n; ++j) rank += tmp[o + j] < (int32_t)f ? 1 : 0;
-    const size_t at = (size_t)o + rank;
-    list[at] = (int32_t)f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int vi = wf_clamp(faces[3 * f + k], V);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) tri[at * 9 + 3 * k + a] = verts[3 * (size_t)vi + a];
-    }
-}
-
+// ---- records -----------------------------------------------------------------------------------------------------------------------
 struct WfFace { double p[3][3], nv[3], area, cen[3]; };
 
 __device__ inline void wf_face(const float *t, WfFace &f) {
@@ -541,15 +340,11 @@ int wf_mesh_args(const char *who, const void *verts, int64_t V, const void *face
 
 extern "C" {
 
-int vt_winding_tree_default_depth(int64_t F) {
-    int L = 1;
-    while (L < VT_WN_MAX_DEPTH && cells_of(L) * 8 < F) ++L;
-    return L;
-}
+int vt_winding_tree_default_depth(int64_t F) { return ot_default_depth(F); }
 
 size_t vt_winding_tree_workspace_bytes(int64_t V, int64_t F, int depth) {
     if (V < 0 || F < 0 || F > MT_MAX_F || V > MT_MAX_V || depth < 1 || depth > VT_WN_MAX_DEPTH) return 0;
-    return wf_work(F, depth).bytes;
+    return ot_work(F, 1, depth).bytes;
 }
 
 int vt_winding_tree_count(const float *verts, int64_t V, const int32_t *faces, int64_t F, int depth, void *workspace, size_t workspace_bytes,
@@ -557,49 +352,18 @@ int vt_winding_tree_count(const float *verts, int64_t V, const int32_t *faces, i
     const char *who = "vt_winding_tree_count: bad argument";
     if (int rc = wf_mesh_args(who, verts, V, faces, F, depth)) return rc;
     if (!workspace) return vt_fail(VT_ERR_INVALID, who);
-    const WfWork w = wf_work(F, depth);
+    const OtWork w = ot_work(F, 1, depth);
     if (workspace_bytes < w.bytes) return vt_fail(VT_ERR_WORKSPACE, "vt_winding_tree_count: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = static_cast<char *>(workspace);
-    int32_t *state = reinterpret_cast<int32_t *>(ws);
-    hipLaunchKernelGGL(wf_init_kernel, dim3(1), dim3(64), 0, st, state);
-    if (F == 0) return vt_check(hipGetLastError(), "vt_winding_tree_count");
-    int32_t *codes = reinterpret_cast<int32_t *>(ws + w.codes), *cnt = reinterpret_cast<int32_t *>(ws + w.cnt);
-    int32_t *doff = reinterpret_cast<int32_t *>(ws + w.doff), *pyr = reinterpret_cast<int32_t *>(ws + w.pyr);
-    int32_t *bsum = reinterpret_cast<int32_t *>(ws + w.bsum);
-    const unsigned vb = blocks_of(V, MT_THREADS);
-    hipLaunchKernelGGL(wf_bbox_kernel, dim3(vb < 1024u ? vb : 1024u), dim3(MT_THREADS), 0, st, verts, V, state);
-    hipLaunchKernelGGL(wf_frame_kernel, dim3(1), dim3(1), 0, st, state);
-    const int64_t leaf = cells_of(depth);
-    if (int rc = vt_fill32(cnt, 0u, (size_t)leaf * 4, st)) return rc;
-    hipLaunchKernelGGL(wf_code_kernel, dim3(blocks_of(F, MT_THREADS)), dim3(MT_THREADS), 0, st, verts, (int)V, faces, (int)F, depth,
-                       (const int32_t *)state, codes, cnt);
-    for (int l = depth; l >= 0; --l) {
-        const int64_t n = cells_of(l);
-        int32_t *lv = pyr + pyr_off(l);
-        if (l == depth) {
-            const WfLeafOcc pred{cnt};
-            scan_launch(pred, n, bsum, lv, state + WF_W_COUNT + l, st);
-            hipLaunchKernelGGL(wf_mark_empty_kernel<WfLeafOcc>, dim3(blocks_of(n, MT_THREADS)), dim3(MT_THREADS), 0, st, pred, n, lv);
-        } else {
-            const WfInnerOcc pred{pyr + pyr_off(l + 1)};
-            scan_launch(pred, n, bsum, lv, state + WF_W_COUNT + l, st);
-            hipLaunchKernelGGL(wf_mark_empty_kernel<WfInnerOcc>, dim3(blocks_of(n, MT_THREADS)), dim3(MT_THREADS), 0, st, pred, n, lv);
-        }
-    }
-    const unsigned nb = blocks_of(leaf, MT_CHUNK);
-    hipLaunchKernelGGL(wf_vscan_count_kernel, dim3(nb), dim3(MT_THREADS), 0, st, (const int32_t *)cnt, leaf, bsum);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(MT_THREADS), 0, st, bsum, (int)nb, state + WF_W_TOTAL);
-    hipLaunchKernelGGL(wf_vscan_write_kernel, dim3(nb), dim3(MT_THREADS), 0, st, (const int32_t *)cnt, leaf, (const int32_t *)bsum, doff);
+    ot_count_enqueue(WfSource{verts, faces, (int)V, (int)F}, 1, depth, w, static_cast<char *>(workspace), (hipStream_t)stream);
     return vt_check(hipGetLastError(), "vt_winding_tree_count");
 }
 
 int vt_winding_tree_layout(int64_t F, int depth, const int32_t *state_host, size_t *offsets) {
     if (!state_host || !offsets || F < 0) return vt_fail(VT_ERR_INVALID, "vt_winding_tree_layout: bad argument");
     if (depth < 1 || depth > VT_WN_MAX_DEPTH || F > MT_MAX_F) return vt_fail(VT_ERR_UNSUPPORTED, "vt_winding_tree_layout: depth outside [1, 7]");
-    WfTree t;
+    OtTree t;
     if (!wf_tree(F, depth, state_host, t)) return vt_fail(VT_ERR_INVALID, "vt_winding_tree_layout: counts that no tree of this size has");
-    offsets[0] = t.pyr; offsets[1] = t.rec; offsets[2] = t.loff; offsets[3] = t.list; offsets[4] = t.tri; offsets[5] = t.bytes;
+    offsets[0] = t.pyr; offsets[1] = t.rec; offsets[2] = t.loff; offsets[3] = t.list; offsets[4] = t.payload; offsets[5] = t.bytes;
     return 0;
 }
 
@@ -609,39 +373,23 @@ int vt_winding_tree_build(const float *verts, int64_t V, const int32_t *faces, i
     if (int rc = wf_mesh_args(who, verts, V, faces, F, depth)) return rc;
     if (!state_host || !workspace || !tree) return vt_fail(VT_ERR_INVALID, who);
     if (state_host[0] != 0) return vt_fail(VT_ERR_INVALID, "vt_winding_tree_build: a vertex coordinate is not finite");
-    WfTree t;
+    OtTree t;
     if (!wf_tree(F, depth, state_host, t)) return vt_fail(VT_ERR_INVALID, "vt_winding_tree_build: counts that no tree of this size has");
-    const WfWork w = wf_work(F, depth);
+    const OtWork w = ot_work(F, 1, depth);
     if (workspace_bytes < w.bytes || tree_bytes < t.bytes) return vt_fail(VT_ERR_WORKSPACE, "vt_winding_tree_build: workspace or tree too small");
     if (F == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    char *ws = static_cast<char *>(workspace), *tr = static_cast<char *>(tree);
-    const int32_t *state = reinterpret_cast<const int32_t *>(ws);
-    const int32_t *codes = reinterpret_cast<const int32_t *>(ws + w.codes), *doff = reinterpret_cast<const int32_t *>(ws + w.doff);
-    int32_t *cursor = reinterpret_cast<int32_t *>(ws + w.cnt), *tmp = reinterpret_cast<int32_t *>(ws + w.tmp);
-    const int32_t *pyr_src = reinterpret_cast<const int32_t *>(ws + w.pyr);
-    const int32_t *pyr = reinterpret_cast<const int32_t *>(tr + t.pyr);
+    char *tr = static_cast<char *>(tree);
+    ot_build_enqueue(WfSource{verts, faces, (int)V, (int)F}, 1, depth, w, static_cast<char *>(workspace), t, tr, st);
+    const int32_t *pyr = reinterpret_cast<const int32_t *>(tr + t.pyr), *loff = reinterpret_cast<const int32_t *>(tr + t.loff);
+    const float *tri = reinterpret_cast<const float *>(tr + t.payload);
     double *recs = reinterpret_cast<double *>(tr + t.rec);
-    int32_t *loff = reinterpret_cast<int32_t *>(tr + t.loff), *list = reinterpret_cast<int32_t *>(tr + t.list);
-    float *tri = reinterpret_cast<float *>(tr + t.tri);
-    WfBase base;
-    for (int l = 0; l <= WF_LEVELS; ++l) base.v[l] = t.rec_base[l];
-    const int64_t words = pyr_off(depth + 1), leaf = cells_of(depth);
-    const int leaves = state_host[WF_W_COUNT + depth];
-    hipLaunchKernelGGL(wf_header_kernel, dim3(blocks_of(words, MT_THREADS)), dim3(MT_THREADS), 0, st, state, pyr_src, words, base, depth, (int)F, tr,
-                       t.pyr);
-    hipLaunchKernelGGL(wf_list_offsets_kernel, dim3(blocks_of(leaf, MT_THREADS)), dim3(MT_THREADS), 0, st, pyr + pyr_off(depth), doff, leaf, leaves,
-                       (int)F, loff);
-    if (int rc = vt_fill32(cursor, 0u, (size_t)leaf * 4, st)) return rc;
-    const unsigned fb = blocks_of(F, MT_THREADS);
-    hipLaunchKernelGGL(wf_fill_kernel, dim3(fb), dim3(MT_THREADS), 0, st, codes, (int)F, doff, cursor, tmp);
-    hipLaunchKernelGGL(wf_rank_kernel, dim3(fb), dim3(MT_THREADS), 0, st, verts, (int)V, faces, codes, (int)F, doff, (const int32_t *)cursor,
-                       (const int32_t *)tmp, list, tri);
-    hipLaunchKernelGGL(wf_leaf_kernel, dim3(blocks_of(leaf, MT_THREADS)), dim3(MT_THREADS), 0, st, pyr + pyr_off(depth), leaf, (const int32_t *)loff,
-                       (const float *)tri, recs + (size_t)t.rec_base[depth] * WF_REC);
+    const int64_t leaf = cells_of(depth);
+    hipLaunchKernelGGL(wf_leaf_kernel, dim3(blocks_of(leaf, MT_THREADS)), dim3(MT_THREADS), 0, st, pyr + pyr_off(depth), leaf, loff, tri,
+                       recs + (size_t)t.base.v[depth] * WF_REC);
     for (int l = depth - 1; l >= 0; --l)
         hipLaunchKernelGGL(wf_inner_kernel, dim3(blocks_of(cells_of(l), MT_THREADS)), dim3(MT_THREADS), 0, st, pyr + pyr_off(l), pyr + pyr_off(l + 1),
-                           cells_of(l), (const double *)(recs + (size_t)t.rec_base[l + 1] * WF_REC), recs + (size_t)t.rec_base[l] * WF_REC);
+                           cells_of(l), (const double *)(recs + (size_t)t.base.v[l + 1] * WF_REC), recs + (size_t)t.base.v[l] * WF_REC);
     return vt_check(hipGetLastError(), "vt_winding_tree_build");
 }
 
@@ -658,13 +406,13 @@ int vt_winding_tree_query(const void *tree, size_t tree_bytes, int64_t F, int de
         return stats ? vt_fill32(stats, 0u, (size_t)N * 8, st) : 0;
     }
     if (!tree || !state_host) return vt_fail(VT_ERR_INVALID, who);
-    WfTree t;
+    OtTree t;
     if (!wf_tree(F, depth, state_host, t)) return vt_fail(VT_ERR_INVALID, "vt_winding_tree_query: counts that no tree of this size has");
     if (tree_bytes < t.bytes) return vt_fail(VT_ERR_WORKSPACE, "vt_winding_tree_query: tree too small");
     const char *walk = getenv("VTACO_WINDING_WALK");
     auto kernel = walk && !strcmp(walk, "skip") ? wf_query_kernel<true> : wf_query_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3(blocks_of(N, MT_THREADS)), dim3(MT_THREADS), 0, st, static_cast<const char *>(tree), t.pyr, t.rec, t.loff,
-                       t.tri, depth, pts, N, accuracy * accuracy, order, out, out_f64, stats);
+                       t.payload, depth, pts, N, accuracy * accuracy, order, out, out_f64, stats);
     return vt_check(hipGetLastError(), "vt_winding_tree_query");
 }
 

@@ -9,6 +9,7 @@ import os
 import torch
 
 from ._base import _lib, VtError, check, dev_ptr, stream_ptr, I32, _c
+from ._octree import _Octree, _ws
 
 
 F64 = torch.float64
@@ -48,16 +49,12 @@ def _pose(what, T, B, dev, name):
     return _c(T[None].expand(B, 4, 4) if T.dim() == 2 else T)
 
 
-def _ws(nbytes, dev):
-    return torch.empty((max(int(nbytes), 8) + 7) // 8, dtype=torch.int64, device=dev)
-
-
 def nn_slab_points(N, M, B=1):
     """The targets per slab vt_nn_points uses for N queries and M targets (times B problems): a multiple of 256."""
     return int(_lib.load().vt_nn_points_slab_points(int(N), int(M), int(B)))
 
 
-class PointTree:
+class PointTree(_Octree):
     """The octrees of B target sets with one M (vt_point_tree_build): ``buf`` (the device buffer of all B trees), ``dst`` (the targets,
     float64 [B,M,3]), ``depth``, ``counts`` (occupied cells per level, root first; one list per problem when the build was batched) and
     ``status`` (the builds' status words or-ed: 0 for a built tree).  The accessors alias ``buf``; ``b`` picks the problem."""
@@ -75,34 +72,17 @@ class PointTree:
         self._base = [0]
         for l in range(self.depth + 1):
             self._base.append(self._base[-1] + max(c[l] for c in per))
+        self._stride, self._items, self._leaves = offsets[5], self.n_points, [c[self.depth] for c in per]
 
-    def _view(self, b, at, dtype, numel):
-        size = torch.empty((), dtype=dtype).element_size()
-        at += b * self._offsets[5]
-        return self.buf.view(torch.uint8)[at:at + numel * size].view(dtype)
-
-    def frame(self, b=0):
-        """float64 [4]: the minimum corner and the side."""
-        return self._view(b, 0, F64, 4)
-
-    def pyramid(self, level, b=0):
-        """int32 [8^level]: the rank of an occupied cell among its level's occupied cells in Morton order, or -1."""
-        return self._view(b, self._offsets[0] + 4 * ((8 ** level - 1) // 7), I32, 8 ** level)
+    frame, pyramid, list_offsets, lists = _Octree._frame, _Octree._pyramid, _Octree._list_offsets, _Octree._lists
 
     def boxes(self, level, b=0):
         """float64 [counts[level], 6]: lo[3], hi[3] of the level's occupied cells, in rank order."""
-        return self._view(b, self._offsets[1] + 48 * self._base[level], F64, 6 * self._counts[b][level]).view(-1, 6)
-
-    def list_offsets(self, b=0):
-        return self._view(b, self._offsets[2], I32, self._counts[b][self.depth] + 1)
-
-    def lists(self, b=0):
-        """int32 [M]: the leaves' point indices, leaf after leaf in Morton order, ascending inside a leaf."""
-        return self._view(b, self._offsets[3], I32, self.n_points)
+        return self._view(self._offsets[1] + 48 * self._base[level], F64, 6 * self._counts[b][level], b).view(-1, 6)
 
     def points(self, b=0):
         """float64 [M, 3]: the targets in list order."""
-        return self._view(b, self._offsets[4], F64, 3 * self.n_points).view(-1, 3)
+        return self._view(self._offsets[4], F64, 3 * self.n_points, b).view(-1, 3)
 
 
 def point_tree_default_depth(M):

@@ -11,6 +11,7 @@ import ctypes
 import torch
 
 from ._base import _lib, VtError, check, dev_ptr, stream_ptr, I32, U8, _c
+from ._octree import _ws  # noqa: F401  (ops/refine.py takes it from here)
 
 
 F64 = torch.float64
@@ -53,10 +54,6 @@ def _i32(what, t, n, name):
     if t.dtype != I32 or tuple(t.shape) != (n,):
         raise VtError(f"{what}: {name} must be int32 [{n}] (got {t.dtype} {tuple(t.shape)})")
     return _c(t)
-
-
-def _ws(nbytes, dev):
-    return torch.empty((max(int(nbytes), 8) + 7) // 8, dtype=torch.int64, device=dev)
 
 
 def components(faces, n_vertices, return_rounds=False):

@@ -9,12 +9,13 @@ import ctypes
 import torch
 
 from ._base import _lib, VtError, check, dev_ptr, stream_ptr, I32, _c
+from ._octree import _Octree, _ws
 
 MAX_DEPTH = 7
 REC = 36            # float64 per cell record: p[3], r, N0[3], M1[3][3], M2[6][3], area, faces
 
 
-class Tree:
+class Tree(_Octree):
     """A built tree: ``buf`` (the device buffer), ``depth``, ``counts`` (records per level, root first) and ``n_faces``.  The views
     below alias ``buf``."""
 
@@ -23,41 +24,24 @@ class Tree:
         self._state = state
         self._offsets = offsets
         self.counts = [int(state[1 + l]) for l in range(self.depth + 1)]
-
-    def _view(self, at, dtype, numel):
-        size = torch.empty((), dtype=dtype).element_size()
-        return self.buf.view(torch.uint8)[at:at + numel * size].view(dtype)
+        self._stride, self._items, self._leaves = 0, self.n_faces, [self.counts[self.depth]]
 
     def pyramid(self, level):
-        """int32 [8^level]: the rank of an occupied cell among its level's occupied cells in Morton order, or -1."""
-        return self._view(self._offsets[0] + 4 * ((8 ** level - 1) // 7), I32, 8 ** level)
+        return self._pyramid(level)
+
+    list_offsets = property(_Octree._list_offsets)
+    lists = property(_Octree._lists)
+    frame = property(_Octree._frame)
 
     def records(self, level):
         """float64 [counts[level], 36]."""
         base = sum(self.counts[:level])
         return self._view(self._offsets[1] + 8 * REC * base, torch.float64, REC * self.counts[level]).view(-1, REC)
 
-    @property
-    def list_offsets(self):
-        return self._view(self._offsets[2], I32, self.counts[self.depth] + 1)
-
-    @property
-    def lists(self):
-        return self._view(self._offsets[3], I32, self.n_faces)
-
-    @property
-    def frame(self):
-        """float64 [4]: the minimum corner and the side."""
-        return self._view(0, torch.float64, 4)
-
 
 def default_depth(n_faces):
     """The smallest depth with 8^depth >= n_faces / 8, in [1, 7]."""
     return int(_lib.load().vt_winding_tree_default_depth(int(n_faces)))
-
-
-def _ws(nbytes, dev):
-    return torch.empty((max(int(nbytes), 8) + 7) // 8, dtype=torch.int64, device=dev)
 
 
 def build(verts, faces, depth=None):
