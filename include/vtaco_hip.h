@@ -282,6 +282,21 @@ int vt_decode_mlp_fwd_wide_f16x3(const float *c, int B, int C, const float *pts,
 /*                       respect to the query points (the reference never reads it: SURVEY.md 8a row A14).             */
 size_t vt_decode_wide_save_floats(int64_t total_points, int hidden, int c_dim, int n_blocks);
 size_t vt_decode_wide_gws_floats(int64_t total_points, int hidden, int c_dim, int n_blocks);
+/* Which kernel a wide decode takes and how it is launched, without launching anything (host code: the rule the launchers themselves */
+/* call).  kind: VT_WIDE_KIND_FWD (vt_decode_fwd_wide / _train / vt_decode_mlp_fwd_wide*), VT_WIDE_KIND_BWD (vt_decode_bwd_wide /      */
+/* vt_decode_mlp_bwd_wide), VT_WIDE_KIND_F16X3 (vt_decode_fwd_wide_f16x3*); tactile: the call gives c_img or finger ids;               */
+/* have_workspace (F16X3 only): the call has 16-byte aligned features for the 64 / 32 pipeline -- a workspace of                       */
+/* vt_decode_wide_f16x3_workspace_bytes, or the features themselves (vt_decode_mlp_fwd_wide_f16x3).  Any result pointer may be NULL:   */
+/*   waves        64-lane waves per workgroup               groups       32-point groups per wave that share a weight fragment         */
+/*   pairs        sets of `groups` groups per tile, after the LDS cap     heads_on_c   the heads' partial sums lie over the c planes   */
+/*   tile_points  points per workgroup tile                 grid_cap     the most workgroups a launch takes: tiles beyond it are       */
+/*   pipeline     1: the register-resident 64 / 32 pipeline              walked by the workgroups in a loop (tile += grid)             */
+/* Returns 0, or VT_ERR_INVALID / VT_ERR_UNSUPPORTED where the launcher would refuse the shape.                                        */
+#define VT_WIDE_KIND_FWD   0
+#define VT_WIDE_KIND_BWD   1
+#define VT_WIDE_KIND_F16X3 2
+int vt_decode_wide_form(int hidden, int c_dim, int n_blocks, int tactile, int kind, int64_t total_points, int have_workspace,
+                        int *waves, int *groups, int *pairs, int *heads_on_c, int *tile_points, int *grid_cap, int *pipeline);
 int vt_decode_fwd_wide_train(const float *grid_cl, int B, int R, int C, const float *pts, int64_t N,
                              const float *c_img, const float *blob_wide, int hidden, int n_blocks, int flags, double padding,
                              float *out, float *out2, float *save, void *stream);

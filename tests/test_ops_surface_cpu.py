@@ -64,7 +64,7 @@ SURFACE = {'EMD_EPS_FINAL': ('const', '1e-06'),
                 'grad_out2=None)'),
  'decode_bwd_wide': ('callable',
                      '(grid_shape, blob_t, grad_out, save, pts, hidden, nb, leaky, nearest, padding=0.1, c_img=None, want_grid_grad=True, '
-                     'grad_out2=None)'),
+                     'grad_out2=None, want_rows=False)'),
  'decode_fwd': ('callable',
                 "(grid, blob, pts=None, c_img=None, padding=0.1, lattice=None, want_contact=False, out=None, save=None, precision='f32', wide=None, "
                 'finger_ids=None, finger_feats=None)'),
@@ -72,7 +72,7 @@ SURFACE = {'EMD_EPS_FINAL': ('const', '1e-06'),
  'decode_fwd_wide_train': ('callable', '(grid, blob, pts, c_img, hidden, nb, leaky, nearest, padding=0.1, want_contact=False)'),
  'decode_last_clock': ('callable', '(workgroups=False)'),
  'decode_mlp_bwd': ('callable', '(blob_t, grad_out, save, pts, C=32)'),
- 'decode_mlp_bwd_wide': ('callable', '(blob_t, grad_out, save, pts, c, hidden, nb, leaky)'),
+ 'decode_mlp_bwd_wide': ('callable', '(blob_t, grad_out, save, pts, c, hidden, nb, leaky, want_rows=False)'),
  'decode_mlp_fwd': ('callable', "(c, blob, pts, precision='f32', wide=None)"),
  'decode_mlp_fwd_train': ('callable', '(c, blob, pts)'),
  'decode_mlp_fwd_wide_train': ('callable', '(c, blob, pts, hidden, nb, leaky)'),
@@ -184,9 +184,13 @@ SURFACE = {'EMD_EPS_FINAL': ('const', '1e-06'),
  'winding_number_scenes': ('callable', '(meshes, pts)')}
 
 # public names added since: none by the split -- the shared helpers of ops/nets2d.py are private to that module; the query of the
-# lattice decode's dispatch rule (ops.decode_lattice_form and the names of its results), which the tests of the lattice kernels ask
+# lattice decode's dispatch rule (ops.decode_lattice_form and the names of its results), which the tests of the lattice kernels ask;
+# the same query of the wide decoder's launchers (ops.decode_wide_form and the names of its kinds), for tests/test_decode_wide_f64_gpu.py,
+# which also reads the backward's dN / dH rows (want_rows of decode_bwd_wide / decode_mlp_bwd_wide)
 NEW_SURFACE = {'LATTICE_FORMS': ('const', "('linear', 'brick', 'staged', 'staged2', 'staged3')"),
-               'decode_lattice_form': ('callable', "(R, lattice, padding=0.1, precision='f32', want_contact=False, c_direct=False, C=32)")}
+               'decode_lattice_form': ('callable', "(R, lattice, padding=0.1, precision='f32', want_contact=False, c_direct=False, C=32)"),
+               'WIDE_KINDS': ('const', "('f32', 'bwd', 'f16x3')"),
+               'decode_wide_form': ('callable', "(hidden, c_dim, nb, kind='f32', tactile=False, total=0, workspace=False)")}
 NEW_PUBLIC = set(NEW_SURFACE)
 
 

@@ -220,6 +220,7 @@ SIGNATURES = {
     "vt_decode_mlp_fwd_wide_f16x3": (_I, [_VP, _I, _I, _VP, _I64, _I, _F, _I64, _VP, _I, _I, _I, _VP, _VP, _VP]),
     "vt_decode_wide_save_floats": (_SZ, [_I64, _I, _I, _I]),
     "vt_decode_wide_gws_floats": (_SZ, [_I64, _I, _I, _I]),
+    "vt_decode_wide_form": (_I, [_I, _I, _I, _I, _I, _I64, _I, _IP, _IP, _IP, _IP, _IP, _IP, _IP]),
     "vt_decode_fwd_wide_train": (_I, [_VP, _I, _I, _I, _VP, _I64, _VP, _VP, _I, _I, _I, _D, _VP, _VP, _VP, _VP]),
     "vt_decoder_wide_blob_t_bytes": (_SZ, [_I, _I, _I]),
     "vt_decoder_pack_wide_t": (_I, [ctypes.POINTER(DecoderParams), _VP, _SZ, _VP]),

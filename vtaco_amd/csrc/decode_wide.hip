@@ -697,6 +697,68 @@ int wide_shape_ok(int hidden, int c_dim, int n_blocks, int p_in) {
            n_blocks >= 1 && n_blocks <= VT_MAX_BLOCKS && (p_in == 3 || p_in == 3 + c_dim);
 }
 
+// ---- which kernel a wide decode takes, and its launch shape ---------------------------------------------------------------------
+// The one rule behind wide_fwd_impl, wide_bwd_impl, wideh_fwd_impl and the read-only query vt_decode_wide_form (host code; the only
+// device call is vt_num_cus's property read).  kind: VT_WIDE_KIND_* (0 exact-f32 forward, inference or training; 1 backward;
+// 2 split-f16 forward).  pipe_inputs (split-f16 only): the call has what decode_wide_p_kernel reads -- 16-byte aligned features, the
+// caller's or a workspace for the grid's samples.  The shape is taken as valid (the launchers check it first).
+//   exact f32   one 32-row block per wave: four waves up to 128 wide, eight above -- the forward by hidden, the backward by
+//               max(hidden, c_dim) (its d c rows are blocks of c_dim); tiles of 32 points, at most 8 workgroups per CU
+//   split f16   `pairs` sets of `groups` 32-point groups per tile: the waves a narrow layer leaves over take further sets
+//               (wideh_pairs) as far as the planes fit the LDS; three groups per wave where the eight-wave planes fit, with the heads'
+//               partial sums on top of the c planes where they do not fit beside them (VTACO_WIDE_NG3=0: two groups everywhere);
+//               at most 4 workgroups per CU.  lds > 160 KiB: no launch
+//   pipeline    64 / 32 / <= 5 without tactile columns on given features (VTACO_WIDE_PIPE=0: never): 2 n_blocks + 2 waves, tiles of
+//               32 points, one workgroup per CU
+struct WideForm { int waves, groups, pairs_asked, pairs, heads_on_c, tile_points, grid_cap, pipeline; size_t lds; };
+
+WideForm wide_form(int kind, int hidden, int C, int n_blocks, int p_in, bool pipe_inputs) {
+    WideForm f{};
+    f.groups = 1; f.pairs_asked = f.pairs = 1; f.tile_points = WIDE_PTS;
+    if (kind == VT_WIDE_KIND_FWD) {
+        const int Kp = (p_in + 7) / 8 * 8, rowsA = hidden > Kp ? hidden : Kp;
+        f.waves = hidden <= 128 ? 4 : 8;
+        f.lds = ((size_t)(C + rowsA + hidden) * WIDE_PITCH + (size_t)f.waves * 2 * 2 * 32) * sizeof(float);
+        f.grid_cap = vt_num_cus() * 8;
+        return f;
+    }
+    if (kind == VT_WIDE_KIND_BWD) {
+        const int widest = hidden > C ? hidden : C;
+        f.waves = widest <= 128 ? 4 : 8;
+        f.lds = (size_t)(2 * hidden + C) * WIDE_PITCH * sizeof(float);
+        f.grid_cap = vt_num_cus() * 8;
+        return f;
+    }
+    if (pipe_inputs && wide_pipe_shape(hidden, C, n_blocks, p_in)) {
+        f.pipeline = 1;
+        f.waves = 2 * n_blocks + 2;
+        f.tile_points = WP_PTS;
+        f.lds = wp_lds_bytes(n_blocks);
+        f.grid_cap = vt_num_cus();
+        return f;
+    }
+    const int Kp = (p_in + 15) / 16 * 16;
+    const int waves = hidden <= 128 ? 4 : 8;
+    const int wid = hidden > Kp ? hidden : Kp;
+    // pairs of point groups per tile: what the spare waves can take, as far as the planes fit the LDS
+    int npair = wideh_pairs(waves, hidden / 32);
+    f.pairs_asked = npair;
+    // groups per wave: three where the eight-wave workgroup's planes still fit the LDS (256 / 128: 150 KB with the heads' partial sums on
+    // top of the c planes) -- a fragment out of the L2s then serves 96 points instead of 64; two elsewhere (VTACO_WIDE_NG3=0: two everywhere)
+    auto planes_of = [&](int gp, int np) { return (size_t)2 * gp * np * wideh_pitch(C) + (size_t)2 * gp * np * wideh_pitch(wid); };
+    auto heads_of = [&](int gp) { return (size_t)waves * 2 * 2 * gp * sizeof(float); };
+    static const bool ng3_off = getenv("VTACO_WIDE_NG3") != nullptr && atoi(getenv("VTACO_WIDE_NG3")) == 0;
+    const bool ng3 = waves == 8 && npair == 1 && !ng3_off && planes_of(96, 1) <= 160 * 1024 && heads_of(96) <= (size_t)2 * 96 * wideh_pitch(C);
+    const int gp = ng3 ? 96 : WH_PTS;
+    while (npair > 1 && planes_of(gp, npair) + heads_of(gp) > 150 * 1024) --npair;
+    f.waves = waves; f.groups = ng3 ? 3 : 2; f.pairs = npair;
+    f.heads_on_c = ng3 && planes_of(gp, npair) + heads_of(gp) > 160 * 1024;
+    f.tile_points = gp * npair;
+    f.lds = planes_of(gp, npair) + (f.heads_on_c ? 0 : heads_of(gp));
+    f.grid_cap = vt_num_cus() * 4;
+    return f;
+}
+
 }  // namespace
 
 extern "C" {
@@ -769,9 +831,9 @@ static int wide_fwd_impl(const float *grid_cl, int B, int R, int C, const float 
     a.d.R = R; a.d.nx = lattice_nx; a.d.box = lattice_box; a.d.divisor = (float)(1.0 + padding + 10e-4);
     a.blob = blob; a.H = hidden; a.C = C; a.nb = n_blocks; a.p_in = p_in; a.Kp = (p_in + 7) / 8 * 8; a.leaky = (flags & VT_WIDE_LEAKY) ? 1 : 0; a.nearest = (flags & VT_WIDE_NEAREST) ? 1 : 0;
     a.save = save;
-    const int rowsA = hidden > a.Kp ? hidden : a.Kp;
-    const int waves = hidden <= 128 ? 4 : 8;
-    const size_t lds = ((size_t)(C + rowsA + hidden) * WIDE_PITCH + (size_t)waves * 2 * 2 * 32) * sizeof(float);
+    const WideForm form = wide_form(VT_WIDE_KIND_FWD, hidden, C, n_blocks, p_in, false);
+    const int waves = form.waves;
+    const size_t lds = form.lds;
     bool attr = false;        // (vt_max_dyn_lds keeps the per-device record)
     if (!attr) {
         hipError_t e = vt_max_dyn_lds(reinterpret_cast<const void *>(&decode_wide_kernel<4>), 160 * 1024);
@@ -780,7 +842,7 @@ static int wide_fwd_impl(const float *grid_cl, int B, int R, int C, const float 
         attr = true;
     }
     const uint32_t ntiles = (a.d.total + WIDE_PTS - 1) / WIDE_PTS;
-    const uint32_t cap = (uint32_t)vt_num_cus() * 8u;
+    const uint32_t cap = (uint32_t)form.grid_cap;
     const dim3 grid(ntiles < cap ? ntiles : cap);
     if (waves == 4) hipLaunchKernelGGL(decode_wide_kernel<4>, grid, dim3(256), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(decode_wide_kernel<8>, grid, dim3(512), lds, (hipStream_t)stream, a);
@@ -879,8 +941,9 @@ static int wideh_fwd_impl(const float *grid_cl, int B, int R, int C, const float
     // 64 / 32 / <= 5 without tactile input columns: the weights in registers, the tiles through a pipeline of waves (decode_wide_pipe.inc)
     // on features given per point -- the caller's (c_direct), or the grid's samples left in the caller's workspace by a pre-pass
     // (the pipeline reads the features as 16-byte pieces: a feature tensor or workspace that is not 16-byte aligned keeps the streaming kernel)
-    if (wide_pipe_shape(hidden, C, n_blocks, p_in) &&
-        (c_direct ? ((size_t)c_direct & 15) == 0 : (ws && ((size_t)ws & 15) == 0 && ws_bytes >= (size_t)a.d.total * C * sizeof(float)))) {
+    const bool pipe_inputs = c_direct ? ((size_t)c_direct & 15) == 0 : (ws && ((size_t)ws & 15) == 0 && ws_bytes >= (size_t)a.d.total * C * sizeof(float));
+    const WideForm form = wide_form(VT_WIDE_KIND_F16X3, hidden, C, n_blocks, p_in, pipe_inputs);
+    if (form.pipeline) {
         if (!c_direct) {
             // a lattice slab of whole x-plane pairs: the LDS-staged gather of the shipped-shape kernels (vt_st3_sample_lattice: footprints by
             // LDS-DMA, the same corner and FMA order, 30 us per 2^19 points against 43 for the plain gather); anything else the plain gather
@@ -896,10 +959,10 @@ static int wideh_fwd_impl(const float *grid_cl, int B, int R, int C, const float
             }
             a.d.c_direct = (const float *)ws;
         }
-        const size_t lds = wp_lds_bytes(n_blocks);
+        const size_t lds = form.lds;
         hipError_t e = vt_max_dyn_lds(reinterpret_cast<const void *>(&decode_wide_p_kernel), 160 * 1024);
         if (e != hipSuccess) return vt_check(e, "vt_decode_fwd_wide_f16x3: hipFuncSetAttribute");
-        const uint32_t ntiles = (a.d.total + WP_PTS - 1) / WP_PTS, cap = (uint32_t)vt_num_cus();
+        const uint32_t ntiles = (a.d.total + WP_PTS - 1) / WP_PTS, cap = (uint32_t)form.grid_cap;
 #ifdef VT_DIAG_WP
         {   // (variant build: the stage waves' phase counts of this launch, printed per wave index)
             static unsigned long long *dbg = nullptr;
@@ -922,25 +985,16 @@ static int wideh_fwd_impl(const float *grid_cl, int B, int R, int C, const float
         hipLaunchKernelGGL(decode_wide_p_kernel, dim3(ntiles < cap ? ntiles : cap), dim3((2 * n_blocks + 2) * 64), lds, (hipStream_t)stream, a);
         return vt_check(hipGetLastError(), "vt_decode_fwd_wide_f16x3");
     }
-    const int waves = hidden <= 128 ? 4 : 8;
-    const int wid = hidden > a.Kp ? hidden : a.Kp;
-    // pairs of point groups per tile: what the spare waves can take, as far as the planes fit the LDS
-    int npair = wideh_pairs(waves, hidden / 32);
-    // groups per wave: three where the eight-wave workgroup's planes still fit the LDS (256 / 128: 150 KB with the heads' partial sums on
-    // top of the c planes) -- a fragment out of the L2s then serves 96 points instead of 64; two elsewhere (VTACO_WIDE_NG3=0: two everywhere)
-    auto planes_of = [&](int gp, int np) { return (size_t)2 * gp * np * wideh_pitch(C) + (size_t)2 * gp * np * wideh_pitch(wid); };
-    auto heads_of = [&](int gp) { return (size_t)waves * 2 * 2 * gp * sizeof(float); };
-    static const bool ng3_off = getenv("VTACO_WIDE_NG3") != nullptr && atoi(getenv("VTACO_WIDE_NG3")) == 0;
-    const bool ng3 = waves == 8 && npair == 1 && !ng3_off && planes_of(96, 1) <= 160 * 1024 && heads_of(96) <= (size_t)2 * 96 * wideh_pitch(C);
-    const int gp = ng3 ? 96 : WH_PTS;
-    while (npair > 1 && planes_of(gp, npair) + heads_of(gp) > 150 * 1024) --npair;
-    a.npair = npair;
-    a.heads_on_c = ng3 && planes_of(gp, npair) + heads_of(gp) > 160 * 1024;
-    const int tile_pts = gp * npair;
-    const size_t lds = planes_of(gp, npair) + (a.heads_on_c ? 0 : heads_of(gp));
+    // (waves, groups per wave, pairs of point groups, where the heads' partial sums live: wide_form)
+    const int waves = form.waves;
+    const bool ng3 = form.groups == 3;
+    a.npair = form.pairs;
+    a.heads_on_c = form.heads_on_c;
+    const int tile_pts = form.tile_points;
+    const size_t lds = form.lds;
     if (lds > 160 * 1024) return vt_fail(VT_ERR_UNSUPPORTED, "vt_decode_fwd_wide_f16x3: the activation planes of this shape do not fit the LDS");
     const uint32_t ntiles = (a.d.total + tile_pts - 1) / tile_pts;
-    const uint32_t cap = (uint32_t)vt_num_cus() * 4u;
+    const uint32_t cap = (uint32_t)form.grid_cap;
     const dim3 grid(ntiles < cap ? ntiles : cap);
     auto go = [&](auto kern, int threads) -> int {
         const hipError_t e = vt_max_dyn_lds(reinterpret_cast<const void *>(kern), 160 * 1024);
@@ -1014,6 +1068,24 @@ size_t vt_decode_wide_gws_floats(int64_t total_points, int hidden, int c_dim, in
     return wide_gws_layout((size_t)total_points, hidden, n_blocks).total;
 }
 
+// which kernel a wide decode of this shape takes and how it is launched (wide_form: the launchers' own rule); nothing is launched
+int vt_decode_wide_form(int hidden, int c_dim, int n_blocks, int tactile, int kind, int64_t total_points, int have_workspace,
+                        int *waves, int *groups, int *pairs, int *heads_on_c, int *tile_points, int *grid_cap, int *pipeline) {
+    if (kind < VT_WIDE_KIND_FWD || kind > VT_WIDE_KIND_F16X3 || total_points < 0) return VT_ERR_INVALID;
+    if (total_points >= 0x7fffffffll) return VT_ERR_UNSUPPORTED;
+    if (!wide_shape_ok(hidden, c_dim, n_blocks, tactile ? 3 + c_dim : 3)) return VT_ERR_UNSUPPORTED;
+    const WideForm f = wide_form(kind, hidden, c_dim, n_blocks, kind == VT_WIDE_KIND_BWD ? 3 : (tactile ? 3 + c_dim : 3), have_workspace != 0);
+    if (f.lds > 160 * 1024) return VT_ERR_UNSUPPORTED;
+    if (waves) *waves = f.waves;
+    if (groups) *groups = f.groups;
+    if (pairs) *pairs = f.pairs;
+    if (heads_on_c) *heads_on_c = f.heads_on_c;
+    if (tile_points) *tile_points = f.tile_points;
+    if (grid_cap) *grid_cap = f.grid_cap;
+    if (pipeline) *pipeline = f.pipeline;
+    return 0;
+}
+
 int vt_decode_fwd_wide_train(const float *grid_cl, int B, int R, int C, const float *pts, int64_t N,
                              const float *c_img, const float *blob, int hidden, int n_blocks, int flags, double padding,
                              float *out, float *out2, float *save, void *stream) {
@@ -1073,9 +1145,9 @@ static int wide_bwd_impl(int B, int R, int C, const float *pts, int64_t N, const
     a.blob_t = blob_t; a.save = save; a.grad_out = grad_out; a.grad_out2 = grad_out2; a.gws = gws;
     a.grad_grid = grad_grid_cl; a.grad_cimg = grad_c_img; a.grad_c = grad_c;
     a.H = hidden; a.C = C; a.nb = n_blocks; a.leaky = (flags & VT_WIDE_LEAKY) ? 1 : 0; a.nearest = (flags & VT_WIDE_NEAREST) ? 1 : 0;
-    const int widest = hidden > C ? hidden : C;
-    const int waves = widest <= 128 ? 4 : 8;
-    const size_t lds = (size_t)(2 * hidden + C) * WIDE_PITCH * sizeof(float);
+    const WideForm form = wide_form(VT_WIDE_KIND_BWD, hidden, C, n_blocks, 3, false);
+    const int waves = form.waves;
+    const size_t lds = form.lds;
     bool attr = false;        // (vt_max_dyn_lds keeps the per-device record)
     if (!attr) {
         hipError_t e = vt_max_dyn_lds(reinterpret_cast<const void *>(&decode_wide_bwd_kernel<4>), 160 * 1024);
@@ -1084,7 +1156,7 @@ static int wide_bwd_impl(int B, int R, int C, const float *pts, int64_t N, const
         attr = true;
     }
     const uint32_t ntiles = (a.d.total + WIDE_PTS - 1) / WIDE_PTS;
-    const uint32_t cap = (uint32_t)vt_num_cus() * 8u;
+    const uint32_t cap = (uint32_t)form.grid_cap;
     const dim3 grid(ntiles < cap ? ntiles : cap);
     if (waves == 4) hipLaunchKernelGGL(decode_wide_bwd_kernel<4>, grid, dim3(256), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(decode_wide_bwd_kernel<8>, grid, dim3(512), lds, (hipStream_t)stream, a);

@@ -12,6 +12,25 @@ def _wide_flags(leaky, nearest):
     return (1 if leaky else 0) | (2 if nearest else 0)          # VT_WIDE_LEAKY | VT_WIDE_NEAREST
 
 
+WIDE_KINDS = ("f32", "bwd", "f16x3")        # VT_WIDE_KIND_*
+
+
+def decode_wide_form(hidden, c_dim, nb, kind="f32", tactile=False, total=0, workspace=False):
+    """Which kernel a wide decode takes and its launch shape (vt_decode_wide_form: the launchers' own rule, asked without launching
+    anything): ``kind`` "f32" (the exact forward, inference or training), "bwd" or "f16x3"; ``tactile``: the call gives c_img or finger
+    ids; ``workspace``: a split-f16 call with what the 64 / 32 pipeline reads (what decode_fwd and decode_mlp_fwd give it).  Returns
+    {"waves", "groups", "pairs", "heads_on_c", "tile_points", "grid_cap", "pipeline"}; raises VtError where the launcher would refuse."""
+    if kind not in WIDE_KINDS:
+        raise VtError(f"decode_wide_form: kind must be one of {WIDE_KINDS} (got {kind!r})")
+    keys = ("waves", "groups", "pairs", "heads_on_c", "tile_points", "grid_cap", "pipeline")
+    out = [ctypes.c_int(0) for _ in keys]
+    rc = _lib.load().vt_decode_wide_form(int(hidden), int(c_dim), int(nb), int(bool(tactile)), WIDE_KINDS.index(kind), int(total),
+                                         int(bool(workspace)), *[ctypes.byref(v) for v in out])
+    if rc < 0:
+        raise VtError(f"decode_wide_form: no {kind!r} wide decode of hidden={hidden}, c_dim={c_dim}, n_blocks={nb} (code {rc})")
+    return {k: int(v.value) for k, v in zip(keys, out)}
+
+
 def decode_fwd_wide_train(grid, blob, pts, c_img, hidden, nb, leaky, nearest, padding=0.1, want_contact=False):
     """vt_decode_fwd_wide_train: logits [B,N] (and the contact logits) plus the saved layer inputs (opaque f32 tensor)."""
     lib = _lib.load()
@@ -98,11 +117,16 @@ def _wide_wgrads(save, gws, P, H, C, nb, pts, c_rows, c_img, grad_out, g2):
     return g
 
 
+def _wide_rows(gws, P, H, nb):
+    return {"rows.dN": gws[:(nb + 1) * P * H].view(nb + 1, P, H), "rows.dH": gws[(nb + 1) * P * H:].view(nb, P, H)}
+
+
 def decode_bwd_wide(grid_shape, blob_t, grad_out, save, pts, hidden, nb, leaky, nearest, padding=0.1, c_img=None,
-                    want_grid_grad=True, grad_out2=None):
+                    want_grid_grad=True, grad_out2=None, want_rows=False):
     """vt_decode_bwd_wide + the weight gradients (vt_rows_wgrad over the saved layer inputs and the output gradients the data pass
     leaves).  Returns (grad_grid channels-last strided [B,C,R,R,R] or None, grad_c_img [B,N,C] or None, dict of parameter gradients
-    keyed like split_decoder_grads)."""
+    keyed like split_decoder_grads); with ``want_rows`` the dict also holds "rows.dN" [nb + 1, P, H] and "rows.dH" [nb, P, H], the
+    output gradients the data pass leaves (wide_gws_layout)."""
     lib = _lib.load()
     B, C, R = grid_shape[0], grid_shape[1], grid_shape[2]
     H = int(hidden)
@@ -123,6 +147,8 @@ def decode_bwd_wide(grid_shape, blob_t, grad_out, save, pts, hidden, nb, leaky, 
                                  dev_ptr(gws, "gws"), dev_ptr(ggrid, "grad_grid"), dev_ptr(gimg, "grad_c_img"), stream_ptr()),
           "vt_decode_bwd_wide")
     g = _wide_wgrads(save, gws, P, H, C, int(nb), pts, save[:P * C].view(P, C), c_img, grad_out, g2)
+    if want_rows:
+        g.update(_wide_rows(gws, P, H, int(nb)))
     return (ggrid.permute(0, 4, 1, 2, 3) if ggrid is not None else None), gimg, g
 
 
@@ -143,8 +169,9 @@ def decode_mlp_fwd_wide_train(c, blob, pts, hidden, nb, leaky):
     return out, save
 
 
-def decode_mlp_bwd_wide(blob_t, grad_out, save, pts, c, hidden, nb, leaky):
-    """vt_decode_mlp_bwd_wide + the weight gradients: (grad_c [B,N,C], dict of parameter gradients keyed like split_decoder_grads)."""
+def decode_mlp_bwd_wide(blob_t, grad_out, save, pts, c, hidden, nb, leaky, want_rows=False):
+    """vt_decode_mlp_bwd_wide + the weight gradients: (grad_c [B,N,C], dict of parameter gradients keyed like split_decoder_grads;
+    with ``want_rows`` also "rows.dN" / "rows.dH" as decode_bwd_wide's)."""
     lib = _lib.load()
     grad_out = _c(grad_out.float())
     pts = _c(pts.float())
@@ -158,4 +185,7 @@ def decode_mlp_bwd_wide(blob_t, grad_out, save, pts, c, hidden, nb, leaky):
     check(lib.vt_decode_mlp_bwd_wide(B, C, dev_ptr(pts, "pts"), N, dev_ptr(blob_t, "blob_t"), H, int(nb), _wide_flags(leaky, False),
                                      dev_ptr(grad_out, "grad_out"), None, dev_ptr(save, "save"), dev_ptr(gws, "gws"),
                                      dev_ptr(grad_c, "grad_c"), stream_ptr()), "vt_decode_mlp_bwd_wide")
-    return grad_c, _wide_wgrads(save, gws, P, H, C, int(nb), pts, c.view(P, C), None, grad_out, None)
+    g = _wide_wgrads(save, gws, P, H, C, int(nb), pts, c.view(P, C), None, grad_out, None)
+    if want_rows:
+        g.update(_wide_rows(gws, P, H, int(nb)))
+    return grad_c, g
