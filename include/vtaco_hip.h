@@ -508,6 +508,23 @@ int vt_fusion_dropout_mask(float p_drop, unsigned long long seed, int call, int 
 size_t vt_fusion_saved_bytes_wide(int B, int N, int d_model);
 size_t vt_fusion_bwd_workspace_bytes_wide(int B, int N, int d_model);
 int vt_fusion_dropout_mask_wide(float p_drop, unsigned long long seed, int call, int which, int points, int d_model, float *mask, void *stream);
+/* What a fuser call of B chunks of N points at d_model launches: the rule the vt_fusion_fwd* / vt_fusion_bwd launchers themselves take   */
+/* their decisions from, asked without launching anything (host code; at d_model > 32 it reads the device's compute-unit count).  train:  */
+/* vt_fusion_fwd_train / vt_fusion_bwd, otherwise vt_fusion_fwd / vt_fusion_fwd_ids.  Honours VTACO_FUSION_SCORE_TERMS as the launchers    */
+/* do.  Any result pointer may be NULL:                                                                                                 */
+/*   form              VT_FUSION_FORM_*: FULL all three half products of the scores (training forward, every d_model > 32), HALF_PAIR     */
+/*                     the keys rounded to half (inference, N < 512), F8 rounded keys with the fp8 corrections (inference, N >= 512)      */
+/*   proj_tiles        32-point tiles per wave of the forward projection kernel                                                         */
+/*   inorm_streamed    1: the InstanceNorm kernel that re-reads its chunk (N > 2048, every d_model > 32), 0: the register-cached one      */
+/*   fwd_row_blocks / bwd_row_blocks   workgroups per chunk of the forward (256 rows) / backward (128 rows) N x N passes                 */
+/*   scalev_strided, epilogue_strided (d_model > 32), add_strided (backward), bwd_point_strided (backward, d_model > 32)                 */
+/*                     1: that kernel's grid is at its cap and its workgroups walk the rest in a loop (the backward's: with train)      */
+/* Returns 0, VT_ERR_INVALID (sizes) or VT_ERR_UNSUPPORTED (d_model).                                                                   */
+#define VT_FUSION_FORM_FULL      0
+#define VT_FUSION_FORM_HALF_PAIR 1
+#define VT_FUSION_FORM_F8        2
+int vt_fusion_plan(int B, int N, int d_model, int train, int *form, int *proj_tiles, int *inorm_streamed, int *fwd_row_blocks,
+                   int *bwd_row_blocks, int *scalev_strided, int *epilogue_strided, int *add_strided, int *bwd_point_strided);
 
 /* ------------------------------------------------------------------------- */
 /* Backward of vt_decode_fwd (training).                                        */

@@ -186,11 +186,13 @@ SURFACE = {'EMD_EPS_FINAL': ('const', '1e-06'),
 # public names added since: none by the split -- the shared helpers of ops/nets2d.py are private to that module; the query of the
 # lattice decode's dispatch rule (ops.decode_lattice_form and the names of its results), which the tests of the lattice kernels ask;
 # the same query of the wide decoder's launchers (ops.decode_wide_form and the names of its kinds), for tests/test_decode_wide_f64_gpu.py,
-# which also reads the backward's dN / dH rows (want_rows of decode_bwd_wide / decode_mlp_bwd_wide)
+# which also reads the backward's dN / dH rows (want_rows of decode_bwd_wide / decode_mlp_bwd_wide); the fuser's launch plan
+# (ops.fusion_plan: score form, InstanceNorm kernel, row blocks, capped grids), for tests/test_fusion_f64_gpu.py
 NEW_SURFACE = {'LATTICE_FORMS': ('const', "('linear', 'brick', 'staged', 'staged2', 'staged3')"),
                'decode_lattice_form': ('callable', "(R, lattice, padding=0.1, precision='f32', want_contact=False, c_direct=False, C=32)"),
                'WIDE_KINDS': ('const', "('f32', 'bwd', 'f16x3')"),
-               'decode_wide_form': ('callable', "(hidden, c_dim, nb, kind='f32', tactile=False, total=0, workspace=False)")}
+               'decode_wide_form': ('callable', "(hidden, c_dim, nb, kind='f32', tactile=False, total=0, workspace=False)"),
+               'fusion_plan': ('callable', '(B, N, d_model=32, train=False)')}
 NEW_PUBLIC = set(NEW_SURFACE)
 
 

@@ -69,7 +69,7 @@ def test_ops_voxelize_is_a_submodule_and_ops_gained_no_name():
         assert inspect.isfunction(getattr(ops.voxelize, name)) and not hasattr(ops, name)
     assert not hasattr(ops, "MAX_RES") and "voxelize" in ops.__doc__
     import test_ops_surface_cpu as surface
-    assert surface.NEW_PUBLIC == {"decode_lattice_form", "LATTICE_FORMS", "decode_wide_form", "WIDE_KINDS"}          # the decoders' form queries; nothing of voxelize
+    assert surface.NEW_PUBLIC == {"decode_lattice_form", "LATTICE_FORMS", "decode_wide_form", "WIDE_KINDS", "fusion_plan"}          # the decoders' and the fuser's form queries; nothing of voxelize
     surface.test_no_other_public_name_appeared()                   # the package's public names are still the recorded ones
     surface.test_every_recorded_name_is_there_unchanged()
     from vtaco_amd import _lib

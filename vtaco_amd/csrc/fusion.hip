@@ -120,7 +120,6 @@ __device__ __forceinline__ void fp8_saturating_mode() { __builtin_amdgcn_s_setre
 // the Q/K groups are permuted so that registers 0..7 / 8..15 of lane-half h hold 8 consecutive
 // output columns (16(2g + r/8) + 8h + r%8): exactly one hi and one lo fragment of the split row
 // layout above, written with 16-byte stores.  V keeps the natural order (store_acc16).
-constexpr int PROJ_TILES = 8;                                  // the most 32-point tiles one wave takes (proj_tiles below)
 template <bool DO_Q, bool DO_KV, bool F8>
 __global__ void __launch_bounds__(256)
 fusion_proj_kernel(const float *Xq, const float *Xk, FusionUnitDev u, float *Qd, float *Kd, float *V, int total, XIds xi, int tiles) {
@@ -242,7 +241,6 @@ fusion_proj_kernel(const float *Xq, const float *Xk, FusionUnitDev u, float *Qd,
 // other operand through LDS in 32-row tiles, double-buffered: every streamed byte is fetched once
 // per 256 fixed rows.
 constexpr int FT = 512;                                     // threads per workgroup
-constexpr int FROWS = 256;                                  // fixed rows per workgroup
 constexpr int SROW = 68;                                    // 256-B row + 16 B pad: conflict-free ds_read_b128
 constexpr int STILE = 32 * SROW;
 
@@ -653,7 +651,6 @@ fusion_inorm_relu_kernel(const float *Z, float *out, int N, int pitch = 32) {
 
 // The same for chunks of at most 2048 points (the reference's chunk size): a thread keeps its 16 x 4 values in registers --
 // one read of z instead of three; thread = (row group of 128, channel quad), 16-byte accesses.
-constexpr int IN_ROWS = 16;
 __global__ void __launch_bounds__(1024)
 fusion_inorm_relu_cached_kernel(const float *Z, float *out, int N) {
     __shared__ float red[16][32];
@@ -722,31 +719,16 @@ size_t fusion_layout(int B, int N, FusionWs *ws, char *base) {
     return off;
 }
 
-// tiles per wave of the projection kernel.  At 256 chunks of 2048 points the kernel moves 400 MB in 111 us (3.6 TB/s: its rows are
-// its bound, 8 / 4 / 2 / 1 tiles per wave all give the same time); launches of a few ten thousand points (the training step's) want
-// the workgroups first: 1.29 -> 1.25 ms per unit chain at 64 chunks
-static int proj_tiles(int P) {
-    int t = P / (128 * 1536);
-    return t < 1 ? 1 : t > PROJ_TILES ? PROJ_TILES : t;
-}
-
 // one attention unit: Xq against Xk -> out = relu(IN(Xq + MHA(Xq, Xk, Xk))).  ``Osave`` != null: training forward (w.l / w.s /
 // w.V / w.Z then point into the caller's saved state instead of the scratch workspace, and the dropouts of ``dc`` are applied)
 void run_unit(const float *Xq, const float *Xk, const FusionUnitDev &u, const float *blob, const FusionWs &w,
               float *out, int B, int N, hipStream_t s, float *Osave = nullptr, DropCfg dc = DropCfg{0, 0, 1.0f, 0, 6}, XIds xi = XIds{}) {
-    const int P = B * N, Npad = (N + 31) / 32 * 32;
-    const int ntile = (N + 31) / 32;
-    const int nrb = (N + FROWS - 1) / FROWS;
-    const int tiles = proj_tiles(P);
-    const dim3 pg((P + 128 * tiles - 1) / (128 * tiles)), tg((unsigned)nrb * (unsigned)B);   // see chunk_of_workgroup
-    // the training forward keeps every product (its backward recomputes the scores on the f32 core); inference runs the
-    // fp8-corrected tiles (keys rounded to half, the queries' remainder and both E x V' corrections on fp8 MFMAs) unless
-    // VTACO_FUSION_SCORE_TERMS is set: 3 = all three half products, 2 = the half-pair form with rounded keys (round 2's)
-    static const char *env_terms = getenv("VTACO_FUSION_SCORE_TERMS");
-    const bool full = Osave != nullptr || (env_terms && env_terms[0] == '3');
-    // (chunks of fewer than 512 points keep the half-pair form: with few keys the fp8 corrections' errors do not average out --
-    // 8e-5 on the fused features at N = 33 against 4e-5, 1.4e-5 against 1.7e-5 at N = 2048; tools/probe/fusion_ragged_err.py)
-    const bool f8 = !full && N >= 512 && !(env_terms && env_terms[0] == '2');
+    const int P = B * N;
+    // the score form and every launch shape: fusion_plan (fusion_common.h), the rule vt_fusion_plan reports
+    const FusionPlan f = fusion_plan(B, N, 32, Osave != nullptr);
+    const int ntile = f.ntile, nrb = f.nrb, tiles = f.proj_tiles;
+    const dim3 pg(f.proj_grid), tg((unsigned)nrb * (unsigned)B);   // see chunk_of_workgroup
+    const bool full = f.form == VT_FUSION_FORM_FULL, f8 = f.form == VT_FUSION_FORM_F8;
     if (Xq == Xk) {
         if (f8) hipLaunchKernelGGL((fusion_proj_kernel<true, true, true>), pg, dim3(256), 0, s, Xq, Xk, u, w.Qd, w.Kd, w.V, P, xi, tiles);
         else hipLaunchKernelGGL((fusion_proj_kernel<true, true, false>), pg, dim3(256), 0, s, Xq, Xk, u, w.Qd, w.Kd, w.V, P, xi, tiles);
@@ -767,17 +749,8 @@ void run_unit(const float *Xq, const float *Xk, const FusionUnitDev &u, const fl
         hipLaunchKernelGGL((fusion_expsum_kernel<true, false>), tg, dim3(FT), 0, s, w.Qd, w.Kd, (const float *)nullptr, w.l, N, 1, nrb, B);
         hipLaunchKernelGGL((fusion_expsum_kernel<false, false>), tg, dim3(FT), 0, s, w.Kd, w.Qd, (const float *)w.l, w.s, N, 0, nrb, B);
     }
-    if (f8) {
-        const size_t tot = (size_t)B * ntile * 64;                   // (b, tile, c, kg)
-        size_t g = (tot + 255) / 256;
-        if (g > 8192) g = 8192;
-        hipLaunchKernelGGL(fusion_scalev8_kernel, dim3((unsigned)g), dim3(256), 0, s, w.V, w.s, w.VT, N, ntile, tot);
-    } else {
-        const size_t tot = (size_t)B * ntile * 128;                  // (b, tile, c, kg, k-step)
-        size_t g = (tot + 255) / 256;
-        if (g > 8192) g = 8192;
-        hipLaunchKernelGGL(fusion_scalev_kernel, dim3((unsigned)g), dim3(256), 0, s, w.V, w.s, w.VT, N, ntile, tot);
-    }
+    if (f8) hipLaunchKernelGGL(fusion_scalev8_kernel, dim3(f.scalev_grid), dim3(256), 0, s, w.V, w.s, w.VT, N, ntile, f.scalev_items);
+    else hipLaunchKernelGGL(fusion_scalev_kernel, dim3(f.scalev_grid), dim3(256), 0, s, w.V, w.s, w.VT, N, ntile, f.scalev_items);
     if (Osave)
         hipLaunchKernelGGL((fusion_attend_kernel<true, true, false>), tg, dim3(FT), 0, s, w.Qd, w.Kd, w.VT, w.l, Xq, blob, w.Z, N, ntile, Osave, dc, nrb, B, xi);
     else if (full)
@@ -786,7 +759,7 @@ void run_unit(const float *Xq, const float *Xk, const FusionUnitDev &u, const fl
         hipLaunchKernelGGL((fusion_attend_kernel<false, false, true>), tg, dim3(FT), 0, s, w.Qd, w.Kd, w.VT, w.l, Xq, blob, w.Z, N, ntile, Osave, dc, nrb, B, xi);
     else
         hipLaunchKernelGGL((fusion_attend_kernel<false, false, false>), tg, dim3(FT), 0, s, w.Qd, w.Kd, w.VT, w.l, Xq, blob, w.Z, N, ntile, Osave, dc, nrb, B, xi);
-    if (N <= 128 * IN_ROWS) hipLaunchKernelGGL(fusion_inorm_relu_cached_kernel, dim3(B), dim3(1024), 0, s, w.Z, out, N);
+    if (!f.inorm_streamed) hipLaunchKernelGGL(fusion_inorm_relu_cached_kernel, dim3(B), dim3(1024), 0, s, w.Z, out, N);
     else hipLaunchKernelGGL(fusion_inorm_relu_kernel, dim3(B), dim3(1024), 0, s, w.Z, out, N);
 }
 
@@ -1013,24 +986,21 @@ size_t fusionw_layout(int B, int N, int C, FusionwWs *ws, char *base) {
 template <int C>
 void run_unit_wide(const float *Xq, const float *Xk, const FusionUnitDev &u, const float *pk, const FusionwWs &w, float *out, int B, int N, hipStream_t s,
                    DropCfg dc = DropCfg{0, 0, 1.0f, 0, 8}) {
-    const int P = B * N, ntile = (N + 31) / 32, nrb = (N + FROWS - 1) / FROWS;
-    const dim3 pg((P + 128 * PROJ_TILES - 1) / (128 * PROJ_TILES)), tg((unsigned)nrb * (unsigned)B);
+    const int P = B * N;
+    const FusionPlan f = fusion_plan(B, N, C, false);               // (all three half products whether a backward follows or not)
+    const int ntile = f.ntile, nrb = f.nrb;
+    const dim3 pg(f.proj_grid), tg((unsigned)nrb * (unsigned)B);
     const size_t plds = (size_t)(4 + C / 32) * (C / 2) * 64 * sizeof(float);
     hipLaunchKernelGGL(fusionw_proj_kernel<C>, pg, dim3(256), plds, s, Xq, Xk, u, w.Qd, w.Kd, w.V, P, 1, 1);
     hipLaunchKernelGGL((fusion_expsum_kernel<true, true>), tg, dim3(FT), 0, s, w.Qd, w.Kd, (const float *)nullptr, w.l, N, 1, nrb, B);
     hipLaunchKernelGGL((fusion_expsum_kernel<false, true>), tg, dim3(FT), 0, s, w.Kd, w.Qd, (const float *)w.l, w.s, N, 0, nrb, B);
-    const size_t tot = (size_t)B * ntile * 128;
-    size_t g = (tot + 255) / 256;
-    if (g > 8192) g = 8192;
     for (int sl = 0; sl < C / 32; ++sl) {                            // the attention output, one 32-channel slice of V' at a time
-        hipLaunchKernelGGL(fusion_scalev_kernel, dim3((unsigned)g), dim3(256), 0, s, w.V, w.s, w.VT, N, ntile, tot, C, 32 * sl);
+        hipLaunchKernelGGL(fusion_scalev_kernel, dim3(f.scalev_grid), dim3(256), 0, s, w.V, w.s, w.VT, N, ntile, f.scalev_items, C, 32 * sl);
         hipLaunchKernelGGL((fusion_attend_kernel<false, true, false>), tg, dim3(FT), 0, s, w.Qd, w.Kd, w.VT, w.l, Xq, w.blob, w.Z, N, ntile,
                            w.O + 32 * sl, DropCfg{0, 0, 1.0f, 0, 6}, nrb, B, XIds{}, C);
     }
     FusionwEpi e{pk, pk + (size_t)C * C, pk + (size_t)C * C + 64 * (size_t)C, u.l1b, u.l2b, u.lnw, u.lnb};
-    int eg = (P + 31) / 32;
-    if (eg > vt_num_cus() * 4) eg = vt_num_cus() * 4;
-    hipLaunchKernelGGL(fusionw_epilogue_kernel<C>, dim3(eg), dim3(C * 2), 0, s, Xq, w.O, e, w.Z, P, dc);
+    hipLaunchKernelGGL(fusionw_epilogue_kernel<C>, dim3(f.epilogue_grid), dim3(C * 2), 0, s, Xq, w.O, e, w.Z, P, dc);
     hipLaunchKernelGGL(fusion_inorm_relu_kernel, dim3(B, C / 32), dim3(1024), 0, s, w.Z, out, N, C);
 }
 
@@ -1092,6 +1062,24 @@ extern "C" {
 size_t vt_fusion_workspace_bytes(int B, int N) {
     if (B <= 0 || N <= 0) return 0;
     return fusion_layout(B, N, nullptr, nullptr);
+}
+
+// what a fuser call of this shape launches (fusion_plan: the launchers' own rule); nothing is launched
+int vt_fusion_plan(int B, int N, int d_model, int train, int *form, int *proj_tiles, int *inorm_streamed, int *fwd_row_blocks,
+                   int *bwd_row_blocks, int *scalev_strided, int *epilogue_strided, int *add_strided, int *bwd_point_strided) {
+    if (B <= 0 || N <= 0 || (int64_t)B * N * FW_MAX >= 0x7fffffffll) return VT_ERR_INVALID;
+    if (d_model < 32 || (d_model & 31) || d_model > FW_MAX) return VT_ERR_UNSUPPORTED;
+    const FusionPlan f = fusion_plan(B, N, d_model, train != 0);
+    if (form) *form = f.form;
+    if (proj_tiles) *proj_tiles = f.proj_tiles;
+    if (inorm_streamed) *inorm_streamed = f.inorm_streamed;
+    if (fwd_row_blocks) *fwd_row_blocks = f.nrb;
+    if (bwd_row_blocks) *bwd_row_blocks = f.bwd_nrb;
+    if (scalev_strided) *scalev_strided = f.scalev_strided;
+    if (epilogue_strided) *epilogue_strided = f.epilogue_strided;
+    if (add_strided) *add_strided = f.add_strided;
+    if (bwd_point_strided) *bwd_point_strided = f.bwd_point_strided;
+    return 0;
 }
 
 size_t vt_fusion_workspace_bytes_wide(int B, int N, int d_model) {

@@ -217,7 +217,7 @@ fb_epilogue_bwd_kernel(const float *Xq, const float *O, const float *dZ, const f
 // ---- streamed tiles of the N x N passes ------------------------------------------------------------------------------
 // A workgroup (4 waves) owns 128 fixed rows and streams every row of the other operand through LDS in 32-row tiles,
 // double-buffered: a 64-d row (Q or K, f32), a 32-d payload row and two per-row scalars.  Rows beyond N arrive as zeros.
-constexpr int NT = 256, NFIX = 128;
+constexpr int NT = 256;
 struct StreamTile {
     float qk[32 * QS];
     float pay[32 * PS];
@@ -511,7 +511,7 @@ fb_proj_bwd_kernel(const float *Qf, const float *Kf, const float *nq, const floa
 }
 
 // ---- weight gradients: dW[o][i] = sum_p G[p][o] X[p][i] (K = 0: column sums of G), reduced over 512-point chunks ----------
-constexpr int WCHUNK = 512, WJOBS = 10, WMAX = 2048;
+constexpr int WJOBS = 10, WMAX = 2048;
 struct WJob {
     const float *G, *X;
     float *dst;
@@ -602,8 +602,9 @@ void unit_bwd(int call, const float *Xq, const float *Xk, const float *dOut, con
               int accumulate, const float *blob_f, const float *blob_t, const FusionSaved &sv, const BwdWs &w, float *dXq, float *dXk,
               int B, int N, float p_drop, unsigned long long seed, hipStream_t s) {
     const int P = B * N;
-    const dim3 pg((P + 3) / 4), eg((P + 127) / 128), tg((unsigned)((N + NFIX - 1) / NFIX) * (unsigned)B);
-    const int nrb = (N + NFIX - 1) / NFIX;
+    const FusionPlan f = fusion_plan(B, N, 32, true);               // row blocks and the capped grids: the rule vt_fusion_plan reports
+    const int nrb = f.bwd_nrb;
+    const dim3 pg((P + 3) / 4), eg((P + 127) / 128), tg((unsigned)nrb * (unsigned)B);
     hipLaunchKernelGGL(fb_proj_kernel, pg, dim3(256), 0, s, Xq, Xk, u, w.Qf, w.Kf, w.nq, w.nk, P);
     hipLaunchKernelGGL(fb_inorm_bwd_kernel, dim3(B), dim3(1024), 0, s, (const float *)sv.Z[call], dOut, w.dZ, N);
     const EpiOut eo{w.gXq, w.dO, w.dOs, w.D, w.dR0, w.R, w.dH0, w.Hd, w.dY, w.dy, w.dyxh};
@@ -633,7 +634,7 @@ void unit_bwd(int call, const float *Xq, const float *Xk, const float *dOut, con
     hipLaunchKernelGGL(fb_wgrad_kernel, dim3(nchunk, WJOBS), dim3(256), 0, s, jobs, P, w.partials, nchunk);
     hipLaunchKernelGGL(fb_wreduce_kernel, dim3(WJOBS), dim3(256), 0, s, jobs, (const float *)w.partials, nchunk);
     const size_t n = (size_t)P * 32;
-    const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const unsigned blocks = f.add_grid;
     if (dXk == nullptr) {                                           // self-attention: Xq and Xk are the same tensor
         hipLaunchKernelGGL(fb_add_kernel, dim3(blocks), dim3(256), 0, s, (const float *)w.gXq, (const float *)w.gXk, dXq, n);
     } else {
@@ -890,15 +891,15 @@ template <int C>
 int unit_bwd_wide(int call, const float *Xq, const float *Xk, const float *dOut, const FusionUnitDev &u, const vt_fusion_unit_grads &g,
                   int accumulate, const FusionSaved &sv, const BwdWsW &w, float *dXq, float *dXk, int B, int N, float p_drop,
                   unsigned long long seed, hipStream_t s) {
-    const int P = B * N, nrb = (N + NFIX - 1) / NFIX, cus = vt_num_cus();
+    const FusionPlan f = fusion_plan(B, N, C, true);
+    const int P = B * N, nrb = f.bwd_nrb, pgrid = f.bwd_point_grid, egrid = f.bwd_epi_grid;
     const dim3 tg((unsigned)nrb * (unsigned)B);
-    const int pgrid = (P + 3) / 4 < 2 * cus ? (P + 3) / 4 : 2 * cus;
     const size_t lds_proj = (size_t)(2 * C * 64 + 4 * 2 * C) * 4, lds_epi = (size_t)(C * (C + 1) + 64 * (C + 1) + C * 65 + 4 * (2 * C + 128)) * 4,
                  lds_pb = (size_t)(2 * 64 * C + C * C + 4 * (128 + C)) * 4;
     hipLaunchKernelGGL(fbw_proj_kernel<C>, dim3(pgrid), dim3(256), lds_proj, s, Xq, Xk, u, w.Qf, w.Kf, w.nq, w.nk, P);
     hipLaunchKernelGGL(fb_inorm_bwd_kernel, dim3(B, C / 32), dim3(1024), 0, s, (const float *)sv.Z[call], dOut, w.dZ, N, C);
     const EpiOut eo{w.gXq, w.dO, w.dOs, w.D, w.dR0, w.R, w.dH0, w.Hd, w.dY, w.dy, w.dyxh};
-    hipLaunchKernelGGL(fbw_epilogue_bwd_kernel<C>, dim3(pgrid < cus ? pgrid : cus), dim3(256), lds_epi, s, Xq, (const float *)sv.O[call], (const float *)w.dZ,
+    hipLaunchKernelGGL(fbw_epilogue_bwd_kernel<C>, dim3(egrid), dim3(256), lds_epi, s, Xq, (const float *)sv.O[call], (const float *)w.dZ,
                        (const float *)sv.linv[call], u, eo, P, drop_cfg(p_drop, seed, (uint32_t)call, 8));
     for (int sl = 0; sl < C / 32; ++sl)
         hipLaunchKernelGGL(fb_dv_kernel, tg, dim3(NT), 0, s, (const float *)w.Qf, (const float *)w.Kf, (const float *)w.dOs,
@@ -916,7 +917,7 @@ int unit_bwd_wide(int call, const float *Xq, const float *Xk, const float *dOut,
         hipLaunchKernelGGL(fb_dk_kernel, tg, dim3(NT), 0, s, (const float *)w.Qf, (const float *)w.Kf, (const float *)w.dO,
                            (const float *)sv.V[call], (const float *)sv.s[call], (const float *)w.tp, (const float *)sv.linv[call],
                            (const float *)w.u, w.dK, N, nrb, B, C, 32 * sl, sl == 0);
-    hipLaunchKernelGGL(fbw_proj_bwd_kernel<C>, dim3(pgrid < cus ? pgrid : cus), dim3(256), lds_pb, s, (const float *)w.Qf, (const float *)w.Kf,
+    hipLaunchKernelGGL(fbw_proj_bwd_kernel<C>, dim3(egrid), dim3(256), lds_pb, s, (const float *)w.Qf, (const float *)w.Kf,
                        (const float *)w.nq, (const float *)w.nk, w.dQ, w.dK, (const float *)w.dV, u, w.gXq, w.gXk, P);
     // weight gradients: dW [M][K] = sum_p G[p][m] X[p][k] (+ db = column sums of G)
     auto wgrad = [&](const float *G, int M, const float *X, int K, float *dW, float *db) -> int {
@@ -943,7 +944,7 @@ int unit_bwd_wide(int call, const float *Xq, const float *Xk, const float *dOut,
     hipLaunchKernelGGL(fbw_colsum_kernel, dim3(nchunk), dim3(256), 0, s, (const float *)w.dy, C, P, w.colp);
     hipLaunchKernelGGL(fbw_colsum_reduce_kernel, dim3(1), dim3(256), 0, s, (const float *)w.colp, C, nchunk, g.norm2_b, accumulate);
     const size_t n = (size_t)P * C;
-    const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const unsigned blocks = f.add_grid;
     if (dXk == nullptr) {
         hipLaunchKernelGGL(fb_add_kernel, dim3(blocks), dim3(256), 0, s, (const float *)w.gXq, (const float *)w.gXk, dXq, n);
     } else {

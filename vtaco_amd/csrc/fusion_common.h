@@ -1,6 +1,8 @@
 // Shared by the TransformerFusion forward (fusion.hip) and backward (fusion_bwd.hip) kernels: the epilogue weight
 // blob, the train-mode dropout rule and the layout of what the training forward leaves for the backward.
 #pragma once
+#include <stdlib.h>
+
 #include "decode_common.h"
 
 namespace {
@@ -124,6 +126,73 @@ __device__ __forceinline__ void chunk_of_workgroup(int nrb, int B, int &rb, int 
         rb = (int)(w % (unsigned)nrb);
         b = (int)(w / (unsigned)nrb);
     }
+}
+
+// ---- the launch plan of one attention unit ---------------------------------------------------------------------------------------
+// The one rule behind run_unit, run_unit_wide (fusion.hip), unit_bwd, unit_bwd_wide (fusion_bwd.hip) and the read-only query
+// vt_fusion_plan (host code; the only device call is vt_num_cus's property read, at d_model > 32).  The tile sizes the kernels are
+// written for:
+constexpr int FROWS = 256;          // forward: fixed rows per workgroup of the N x N passes
+constexpr int NFIX = 128;           // backward: fixed rows per workgroup of the N x N passes
+constexpr int WCHUNK = 512;         // backward: points per partial weight gradient (chunks run over scene boundaries)
+constexpr int IN_ROWS = 16;         // fusion_inorm_relu_cached_kernel: 128 x IN_ROWS points in registers
+constexpr int PROJ_TILES = 8;       // the most 32-point tiles one wave of the projection kernel takes
+constexpr int SCALEV_CAP = 8192, ADD_CAP = 4096;     // the most workgroups of fusion_scalev[8]_kernel / fb_add_kernel (grid-stride beyond)
+struct FusionPlan {
+    int form;                       // VT_FUSION_FORM_*: the score / E x V' operands of the forward
+    int ntile, nrb, bwd_nrb;        // 32-point tiles and forward / backward row blocks per chunk
+    int proj_tiles, proj_grid;      // 32-point tiles per wave and workgroups (of four waves) of the forward projection
+    int inorm_streamed;             // 1: fusion_inorm_relu_kernel, 0: fusion_inorm_relu_cached_kernel
+    size_t scalev_items;            // work items of fusion_scalev_kernel (128 per tile) / fusion_scalev8_kernel (64 per tile)
+    unsigned scalev_grid;
+    int epilogue_grid;              // d_model > 32: workgroups of fusionw_epilogue_kernel (32 points each per round); 0 at d_model 32
+    unsigned add_grid;              // backward: workgroups of fb_add_kernel (256 elements each per round)
+    int bwd_point_grid, bwd_epi_grid;   // d_model > 32: workgroups (4 points each per round) of the backward's projection / epilogue kernels
+    bool scalev_strided, epilogue_strided, add_strided, bwd_point_strided;
+};
+// tiles per wave of the projection kernel.  At 256 chunks of 2048 points the kernel moves 400 MB in 111 us (3.6 TB/s: its rows are
+// its bound, 8 / 4 / 2 / 1 tiles per wave all give the same time); launches of a few ten thousand points (the training step's) want
+// the workgroups first: 1.29 -> 1.25 ms per unit chain at 64 chunks
+inline int proj_tiles(int P) {
+    int t = P / (128 * 1536);
+    return t < 1 ? 1 : t > PROJ_TILES ? PROJ_TILES : t;
+}
+// train: the call keeps the state for a backward (vt_fusion_fwd_train).  The training forward keeps every product (its backward
+// recomputes the scores on the f32 core) and so does every call at d_model > 32; inference at d_model 32 runs the fp8-corrected tiles
+// (keys rounded to half, the queries' remainder and both E x V' corrections on fp8 MFMAs) unless VTACO_FUSION_SCORE_TERMS is set:
+// 3 = all three half products, 2 = the half-pair form with rounded keys (round 2's).
+// (chunks of fewer than 512 points keep the half-pair form: with few keys the fp8 corrections' errors do not average out --
+// 8e-5 on the fused features at N = 33 against 4e-5, 1.4e-5 against 1.7e-5 at N = 2048; tools/probe/fusion_ragged_err.py)
+inline FusionPlan fusion_plan(int B, int N, int C, bool train) {
+    static const char *env_terms = getenv("VTACO_FUSION_SCORE_TERMS");
+    FusionPlan f{};
+    const int P = B * N;
+    const bool wide = C > 32;
+    const bool full = wide || train || (env_terms && env_terms[0] == '3');
+    const bool f8 = !full && N >= 512 && !(env_terms && env_terms[0] == '2');
+    f.form = full ? VT_FUSION_FORM_FULL : f8 ? VT_FUSION_FORM_F8 : VT_FUSION_FORM_HALF_PAIR;
+    f.ntile = (N + 31) / 32;
+    f.nrb = (N + FROWS - 1) / FROWS;
+    f.bwd_nrb = (N + NFIX - 1) / NFIX;
+    f.proj_tiles = wide ? PROJ_TILES : proj_tiles(P);
+    f.proj_grid = (P + 128 * f.proj_tiles - 1) / (128 * f.proj_tiles);
+    f.inorm_streamed = wide || N > 128 * IN_ROWS;
+    f.scalev_items = (size_t)B * f.ntile * (f8 ? 64 : 128);      // f8: (b, tile, c, kg); otherwise (b, tile, c, kg, k-step)
+    const size_t sg = (f.scalev_items + 255) / 256;
+    f.scalev_strided = sg > (size_t)SCALEV_CAP;
+    f.scalev_grid = (unsigned)(f.scalev_strided ? SCALEV_CAP : sg);
+    const size_t ag = ((size_t)P * C + 255) / 256;                  // (the backward's grids: of a call that keeps the state for one)
+    f.add_strided = train && ag > (size_t)ADD_CAP;
+    f.add_grid = (unsigned)(f.add_strided ? ADD_CAP : ag);
+    if (wide) {
+        const int cus = vt_num_cus(), eg = (P + 31) / 32, pg = (P + 3) / 4;
+        f.epilogue_strided = eg > cus * 4;
+        f.epilogue_grid = f.epilogue_strided ? cus * 4 : eg;
+        f.bwd_point_grid = pg < 2 * cus ? pg : 2 * cus;
+        f.bwd_epi_grid = f.bwd_point_grid < cus ? f.bwd_point_grid : cus;
+        f.bwd_point_strided = train && pg > f.bwd_epi_grid;
+    }
+    return f;
 }
 
 inline FusionUnitDev unit_of(const vt_fusion_unit &u) {

@@ -23,9 +23,29 @@ def _fusion_params(self_attn, cross_attn, C, keep):
     return prm
 
 
+def fusion_plan(B, N, d_model=32, train=False):
+    """What a fuser call of ``B`` chunks of ``N`` points launches (vt_fusion_plan: the launchers' own rule, asked without launching
+    anything; VTACO_FUSION_SCORE_TERMS counts as it does for them).  ``train``: fusion_fwd_train / fusion_bwd, otherwise fusion_fwd /
+    fusion_fwd_ids.  Returns {"form": "full" | "half_pair" | "f8", "proj_tiles", "inorm": "cached" | "streamed", "fwd_row_blocks",
+    "bwd_row_blocks", "strided": the names among ("scalev", "epilogue", "add", "bwd_point") of the capped grids whose workgroups
+    walk the rest in a loop}; raises VtError where the launchers would refuse the shape."""
+    keys = ("form", "proj_tiles", "inorm", "fwd_row_blocks", "bwd_row_blocks", "scalev", "epilogue", "add", "bwd_point")
+    out = [ctypes.c_int(0) for _ in keys]
+    rc = _lib.load().vt_fusion_plan(int(B), int(N), int(d_model), int(bool(train)), *[ctypes.byref(v) for v in out])
+    if rc < 0:
+        raise VtError(f"fusion_plan: no fuser call of B={B}, N={N}, d_model={d_model} (code {rc})")
+    v = {k: int(x.value) for k, x in zip(keys, out)}
+    return {"form": ("full", "half_pair", "f8")[v["form"]], "proj_tiles": v["proj_tiles"], "inorm": ("cached", "streamed")[v["inorm"]],
+            "fwd_row_blocks": v["fwd_row_blocks"], "bwd_row_blocks": v["bwd_row_blocks"],
+            "strided": tuple(k for k in ("scalev", "epilogue", "add", "bwd_point") if v[k])}
+
+
 def fusion_fwd(c_img, c, self_attn, cross_attn):
     """TransformerFusion forward, eval mode (vt_fusion_fwd).  ``self_attn`` / ``cross_attn``:
-    dicts with the ten tensors of a vt_fusion_unit."""
+    dicts with the ten tensors of a vt_fusion_unit.
+
+    A chunk of ONE point (N = 1) gives zeros, here and in every other entry of this module: the InstanceNorm over the chunk sees
+    z - mean = 0 and a variance of 0, as the oracle's restatement does; torch's own InstanceNorm1d refuses a single element."""
     lib = _lib.load()
     c_img, c = _c(c_img.float()), _c(c.float())
     B, N, C = c.shape
