@@ -1904,6 +1904,41 @@ int vt_refine(const float *grid_cl, int R, int C, float *verts, int64_t V, const
               uint64_t first_step, const float *eps_given, float *sq, int composed_jet, float *terms, void *workspace, size_t workspace_bytes,
               void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------ */
+/* k nearest points of a point set, and normals from them (csrc/knn.hip; DESIGN.md section "knn.hip"; tests/knn_ref.py restates it in     */
+/* numpy).  Stands where the reference asks pykdtree for k neighbours (get_nearest_neighbors_indices_batch, src/common.py:158-175) and     */
+/* where its visualize_pointcloud is handed normals (src/utils/visualize.py:51).  Everything is float64 in a fixed order; no atomics;      */
+/* run-to-run equal bits.  src [B][N][3], dst [B][M][3], T [B][4][4] or NULL (applied to src first, vt_nn_points' arithmetic).            */
+/* The result, for both searches: per query the k targets smallest in the order (d2, index), d2 = (dx dx + dy dy) + dz dz, written         */
+/*   ascending to d2 [B][N][k] f64 and idx [B][N][k] i32.  The list starts as k entries (+inf, -1); a target is taken when                 */
+/*   d < worst || (d == worst && m < worst_m), worst the list's last entry.  With M < k the tail stays (+inf, -1); a query with a NaN or   */
+/*   an infinite coordinate returns all (+inf, -1).  1 <= k <= VT_KNN_MAX_K.  k = 1 is vt_nn_points bit for bit.                            */
+/*   vt_knn_points       every target per query: 256 queries per workgroup and one slab of targets, one partial list per (query, slab)     */
+/*                       in the workspace, a finish pass that merges them in ascending slab order.  slab_points: 0 for                    */
+/*                       vt_knn_points_slab_points(N, M, B), else a multiple of 256; no result depends on it.  workspace:                  */
+/*                       vt_knn_points_workspace_bytes(N, M, B, k, slab_points) (0 for arguments outside the limits).                      */
+/*   vt_point_tree_knn   the same lists, bit for bit, from vt_point_tree_query's walk of a built point tree (tree, depth, state_host as    */
+/*                       there): a cell is skipped exactly when its box's lower bound exceeds worst, which is +inf until the list holds    */
+/*                       k targets.  stats, perm and VTACO_POINT_TREE_WALK as for vt_point_tree_query.                                     */
+/*   vt_knn_normals      pts [B][M][3], idx [B][N][k] (entries outside [0, M) are left out) -> normal [B][N][3]: the unit eigenvector of    */
+/*                       the smallest eigenvalue of the neighbours' covariance (centroid and covariance in ascending slot order, by        */
+/*                       differences from the first valid neighbour; divided by the count; cyclic Jacobi with a fixed sweep count), eig    */
+/*                       [B][N][3]: the eigenvalues ascending.  view NULL: the normal's component of largest magnitude is positive (the    */
+/*                       lowest axis among equals); view [B][3] (view_per_point == 0) or [B][N][3]: negated when                          */
+/*                       n . (view - pts[idx[..][0]]) < 0.  Fewer than 3 valid neighbours or an exactly zero covariance: zeros.            */
+/* All are asynchronous, allocate nothing and read nothing back.  Errors, all before any launch: a NULL array, N or M < 1, B outside       */
+/*   [1, 65535] or a slab_points that is no multiple of 256 is VT_ERR_INVALID; k outside [1, VT_KNN_MAX_K] VT_ERR_UNSUPPORTED; a short      */
+/*   workspace VT_ERR_WORKSPACE.                                                                                                          */
+#define VT_KNN_MAX_K 32
+size_t vt_knn_points_workspace_bytes(int64_t N, int64_t M, int B, int k, int slab_points);
+int vt_knn_points_slab_points(int64_t N, int64_t M, int B);
+int vt_knn_points(const double *src, int64_t N, const double *dst, int64_t M, int B, const double *T, int k, int slab_points, double *d2, int32_t *idx,
+                  void *workspace, size_t workspace_bytes, void *stream);
+int vt_point_tree_knn(const void *tree, size_t tree_bytes, int64_t M, int depth, int B, const int32_t *state_host, const double *src, int64_t N,
+                      const double *T, int k, double *d2, int32_t *idx, int32_t *stats, const int32_t *perm, void *stream);
+int vt_knn_normals(const double *pts, int64_t M, const int32_t *idx, int64_t N, int k, int B, const double *view, int view_per_point, double *normal,
+                   double *eig, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

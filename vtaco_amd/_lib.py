@@ -430,6 +430,11 @@ SIGNATURES = {
     "vt_point_tree_lanes": (_I, [_VP, _SZ, _I64, _I, _I, _VP, _VP, _I64, _VP, _VP, _VP, _SZ, _VP]),
     "vt_icp_tree_workspace_bytes": (_SZ, [_I64, _I, _I]),
     "vt_icp_tree": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _SZ, _I, _VP, _I, _VP, _I, _D, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_knn_points_workspace_bytes": (_SZ, [_I64, _I64, _I, _I, _I]),
+    "vt_knn_points_slab_points": (_I, [_I64, _I64, _I]),
+    "vt_knn_points": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _I, _I, _VP, _VP, _VP, _SZ, _VP]),         # get_nearest_neighbors_indices_batch, common.py:158-175
+    "vt_point_tree_knn": (_I, [_VP, _SZ, _I64, _I, _I, _VP, _VP, _I64, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "vt_knn_normals": (_I, [_VP, _I64, _VP, _I64, _I, _I, _VP, _I, _VP, _VP, _VP]),                  # the normals of visualize_pointcloud, utils/visualize.py:51
     "vt_mesh_components_workspace_bytes": (_SZ, [_I64, _I64]),
     "vt_mesh_components": (_I, [_VP, _I64, _I64, _VP, _IP, _VP, _SZ, _VP]),                           # trimesh graph.connected_components
     "vt_mesh_component_table_workspace_bytes": (_SZ, [_I64, _I64]),

@@ -201,3 +201,50 @@ def contact_clouds_on_device(depths_dev, origin_dev, cam_pos, cam_rot, pc_ply, t
                        torch.from_numpy(row0).to(dev), torch.from_numpy(pose).to(dev), width, height, fov, max_points, p_sample)
     return p_sample, finger
 
+
+
+KNN_MAX_K = 32      # VT_KNN_MAX_K, the longest neighbour list csrc/knn.hip keeps
+
+
+def _knn_device(src, dst, k, method):
+    """(d2 [B,N,k] f64, idx [B,N,k] i32) as numpy arrays from ``ops.knn.knn_points`` on the current HIP device; src [B,N,3], dst [B,M,3]
+    float64 numpy.  The one place ``get_nearest_neighbors_indices_batch`` touches the device."""
+    import torch
+
+    from . import ops
+    dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")      # a CPU tensor raises VtError
+    d2, idx = ops.knn.knn_points(torch.from_numpy(src).to(dev), torch.from_numpy(dst).to(dev), k, method=method)
+    return d2.cpu().numpy(), idx.cpu().numpy()
+
+
+def get_nearest_neighbors_indices_batch(points_src, points_tgt, k=1, method='brute'):
+    """(indices, distances): per batch element the k nearest points of ``points_tgt[b]`` to every point of ``points_src[b]``
+    (src/common.py:158-175, pykdtree's ``query(k)`` there), as two lists of numpy arrays, int64 [N] and float64 [N] for k == 1, else
+    [N,k], ascending by (distance, index).  Distances are Euclidean: the float64 square root of csrc/knn.hip's squared distance.  The
+    batches are sequences of numpy arrays or tensors [N_b,3]; elements of one size run as one launch, elements of different sizes one by
+    one.  ``method``: 'brute' or 'tree' (``ops.knn.knn_points``).  Where the target has fewer than k points the tail is (-1, inf)."""
+    import numpy as np
+
+    from ._lib import VtError
+    if isinstance(k, bool) or int(k) != k or int(k) < 1:
+        raise VtError(f"get_nearest_neighbors_indices_batch: k must be an integer >= 1 (got {k!r})")
+    k = int(k)
+    if k > KNN_MAX_K:
+        raise VtError(f"get_nearest_neighbors_indices_batch: k = {k} is above the cap of {KNN_MAX_K} neighbours the device lists hold (VT_KNN_MAX_K)")
+    host = lambda x: np.ascontiguousarray(x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x), dtype=np.float64)
+    src, tgt = [host(p) for p in points_src], [host(p) for p in points_tgt]
+    if len(src) != len(tgt):
+        raise VtError(f"get_nearest_neighbors_indices_batch: {len(src)} source sets for {len(tgt)} target sets")
+    if any(p.ndim != 2 or p.shape[1] != 3 for p in src + tgt):
+        raise VtError("get_nearest_neighbors_indices_batch: every batch element must be [N,3]")
+    if src and len({p.shape for p in src}) == 1 and len({p.shape for p in tgt}) == 1:
+        d2, idx = _knn_device(np.stack(src), np.stack(tgt), k, method)
+    else:
+        parts = [_knn_device(s[None], t[None], k, method) for s, t in zip(src, tgt)]
+        d2, idx = [p[0][0] for p in parts], [p[1][0] for p in parts]
+    indices, distances = [], []
+    for b in range(len(src)):
+        i, d = np.asarray(idx[b]).astype(np.int64), np.sqrt(np.asarray(d2[b], dtype=np.float64))
+        indices.append(i[:, 0] if k == 1 else i)
+        distances.append(d[:, 0] if k == 1 else d)
+    return indices, distances

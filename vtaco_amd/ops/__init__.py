@@ -14,9 +14,10 @@ This file only re-exports: callers write ``ops.name`` and look the name up at ca
 ``ops.mesh.cluster_faces``, ``ops.mesh.cluster_place``.  ``winding`` is a submodule only too: ``ops.winding.build``, ``ops.winding.query``,
 ``ops.winding.fast``, ``ops.winding.query_scenes`` (the exact sum stays ``ops.winding_number``), and so is ``rays``: ``ops.rays.ray_mesh``,
 ``ops.rays.ray_tree_query``, ``ops.rays.camera_rays``, ``ops.rays.depth_from_hits``; and ``refine``: ``ops.refine.decode_jet``, ``ops.refine.refine_sample``,
-``ops.refine.refine_face_grad``, ``ops.refine.refine_step``, ``ops.refine.refine``.
+``ops.refine.refine_face_grad``, ``ops.refine.refine_step``, ``ops.refine.refine``; and ``knn``: ``ops.knn.knn_points``, ``ops.knn.knn_slab_points``,
+``ops.knn.normals``.
 """
-from . import (_base, decode, decode_train, decode_wide, fusion, icp, labels, mano, mc, mesh, metrics, mise, nets2d, planes, pointnet, points, rays, refine, resnet_bneck, resnet_train, touch,  # noqa: F401
+from . import (_base, decode, decode_train, decode_wide, fusion, icp, knn, labels, mano, mc, mesh, metrics, mise, nets2d, planes, pointnet, points, rays, refine, resnet_bneck, resnet_train, touch,  # noqa: F401
                unet3d, voxel, voxel_encoder, voxelize, winding)
 from ._base import *            # noqa: F401,F403
 from ._base import _c, _lib, _ptr_array     # noqa: F401
