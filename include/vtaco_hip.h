@@ -1718,6 +1718,39 @@ size_t vt_mesh_normals_workspace_bytes(int64_t V, int64_t F);
 int vt_mesh_normals(const void *verts, int verts_f64, int64_t V, const int32_t *faces, int64_t F, int weight, void *face_normals,
                     void *vertex_normals, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- mesh hole filling (mesh_fill.hip) --------------------------------------------------------------------------------------------- */
+/* Replaces: trimesh.repair.fill_holes on the meshes the reference wraps in trimesh.Trimesh -- without its limit to 3- and 4-edge       */
+/*   holes.  tests/mesh_fill_ref.py is the definition and the kernels equal it bit for bit ("mesh_fill.hip").  Meshes and    */
+/*   size rules as in the topology block.  Half-edge h = 3 f + k runs from faces[f][k] to faces[f][(k+1)%3]; it is a boundary half-edge */
+/*   when its undirected edge is used by no other half-edge.  succ(h): the boundary half-edge that leaves head(h) when exactly one      */
+/*   leaves and one enters that vertex; a loop is a cycle of succ; the boundary half-edges on no cycle are `irregular`.  Loops are      */
+/*   numbered by their smallest half-edge, and start there.                                                                              */
+/* vt_mesh_boundary: the edge table, the boundary half-edges compacted in half-edge order and succ over them, left in the workspace     */
+/*   (vt_mesh_boundary_workspace_bytes(V, F) bytes) for vt_mesh_boundary_loops; *n_boundary = NB.  Waits for the stream (one read; a    */
+/*   face index outside [0, V) makes it VT_ERR_INVALID; NB = 0 launches nothing further).                                               */
+/* vt_mesh_boundary_loops: on the workspace vt_mesh_boundary left for the same faces, NB >= 1 its count.  Pointer doubling (ceil(log2   */
+/*   NB) rounds for the loop's smallest element, as many for the position; enqueued at once), then loop_offsets [L+1] (capacity NB+1),  */
+/*   loop_vertices and loop_half_edges [NB - n_irregular] (capacity NB): loop l owns [loop_offsets[l], loop_offsets[l+1]), element p    */
+/*   the p-th half-edge after the loop's smallest and its tail vertex.  Waits for the stream (one read: *n_loops, *n_irregular).        */
+/* vt_mesh_fill_count: per loop of n edges, filled when 3 <= n <= max_edges (max_edges 0: no limit): method 0 ('fan') n - 2 faces       */
+/*   (v_0, v_{i+1}, v_i), i = 1 .. n-2; method 1 ('centroid') for n >= 4 one new vertex c and n faces (c, v_{i+1}, v_i), i = 0 .. n-1,  */
+/*   for n = 3 the one face (v_0, v_2, v_1).  Leaves the loops' face and vertex offsets in the workspace                                 */
+/*   (vt_mesh_fill_workspace_bytes(L) bytes).  Waits for the stream (one read: the three totals).                                       */
+/* vt_mesh_fill_emit (asynchronous): on the workspace vt_mesh_fill_count left for the same loops and method.  out_verts [V +            */
+/*   n_new_verts][3] in the vertices' type and out_faces [F + n_new_faces][3]: the originals copied, then the new faces by (loop, i)    */
+/*   and the new vertices by loop.  c = (the exact fixed-point sum of the loop's coordinates, as vt_mesh_component_stats sums) / n in   */
+/*   float64, rounded to the vertices' type: the bits depend on no order.  F = 0 is allowed here (nothing is copied).                   */
+size_t vt_mesh_boundary_workspace_bytes(int64_t V, int64_t F);
+int vt_mesh_boundary(const int32_t *faces, int64_t F, int64_t V, int *n_boundary, void *workspace, size_t workspace_bytes, void *stream);
+int vt_mesh_boundary_loops(const int32_t *faces, int64_t F, int64_t V, int64_t NB, int32_t *loop_offsets, int32_t *loop_vertices,
+                           int32_t *loop_half_edges, int *n_loops, int *n_irregular, void *workspace, size_t workspace_bytes, void *stream);
+size_t vt_mesh_fill_workspace_bytes(int64_t L);
+int vt_mesh_fill_count(const int32_t *loop_offsets, int64_t L, int method, int64_t max_edges, int *n_filled, int *n_new_faces, int *n_new_verts,
+                       void *workspace, size_t workspace_bytes, void *stream);
+int vt_mesh_fill_emit(const void *verts, int verts_f64, int64_t V, const int32_t *faces, int64_t F, const int32_t *loop_offsets,
+                      const int32_t *loop_vertices, int64_t L, int method, int64_t n_new_faces, int64_t n_new_verts, void *out_verts,
+                      int32_t *out_faces, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------------------------------ */
 /* Fast winding number (csrc/winding_fast.hip; DESIGN.md section "winding_fast.hip"; tests/winding_fast_ref.py restates it in numpy):     */
 /* an octree over the faces' centroids, `depth` levels below the root (1 .. VT_WN_MAX_DEPTH), whose occupied cells carry the dipole       */

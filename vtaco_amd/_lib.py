@@ -455,6 +455,12 @@ SIGNATURES = {
     "vt_mesh_cluster_place": (_I, [_VP, _I, _I64, _VP, _I64, _I, _VP, _VP, _I64, _I, _VP, _VP, _VP, _SZ, _VP]),
     "vt_mesh_normals_workspace_bytes": (_SZ, [_I64, _I64]),
     "vt_mesh_normals": (_I, [_VP, _I, _I64, _VP, _I64, _I, _VP, _VP, _VP, _SZ, _VP]),                   # trimesh face_normals / vertex_normals
+    "vt_mesh_boundary_workspace_bytes": (_SZ, [_I64, _I64]),
+    "vt_mesh_boundary": (_I, [_VP, _I64, _I64, _IP, _VP, _SZ, _VP]),                                    # trimesh repair.fill_holes
+    "vt_mesh_boundary_loops": (_I, [_VP, _I64, _I64, _I64, _VP, _VP, _VP, _IP, _IP, _VP, _SZ, _VP]),
+    "vt_mesh_fill_workspace_bytes": (_SZ, [_I64]),
+    "vt_mesh_fill_count": (_I, [_VP, _I64, _I, _I64, _IP, _IP, _IP, _VP, _SZ, _VP]),
+    "vt_mesh_fill_emit": (_I, [_VP, _I, _I64, _VP, _I64, _VP, _VP, _I64, _I, _I64, _I64, _VP, _VP, _VP, _SZ, _VP]),
     "vt_winding_tree_default_depth": (_I, [_I64]),
     "vt_winding_tree_workspace_bytes": (_SZ, [_I64, _I64, _I]),
     "vt_winding_tree_count": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _SZ, _VP]),

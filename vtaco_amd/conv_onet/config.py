@@ -69,7 +69,8 @@ def get_generator(model, cfg, device, **kwargs):
                        with_img=cfg['model'].get('with_img', False), encode_t2d=cfg['model'].get('encoder_t2d', False),
                        reference_returns=kwargs.get('reference_returns', g.get('reference_returns', False)),
                        extraction=g.get('extraction', 'dense'), components=g.get('components', 'all'),
-                       min_component_faces=g.get('min_component_faces', 0))
+                       min_component_faces=g.get('min_component_faces', 0), fill_holes=g.get('fill_holes'),
+                       fill_holes_max_edges=g.get('fill_holes_max_edges'))
 
 
 def get_trainer(model, optimizer, cfg, device, **kwargs):

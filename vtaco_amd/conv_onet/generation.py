@@ -121,6 +121,21 @@ class Mesh(namedtuple("Mesh", ["vertices", "faces"])):
         from ..utils import mesh_clean
         return mesh_clean.merge_vertices(self, tol=tol, unique_faces=unique_faces)
 
+    def boundary_loops(self):
+        """The boundary loops of the mesh (utils/mesh_clean.py: boundary_loops)."""
+        from ..utils import mesh_clean
+        return mesh_clean.boundary_loops(self)
+
+    def fill_holes(self, method="fan", max_edges=None):
+        """The mesh with its boundary loops capped; the mesh itself when it has none (utils/mesh_clean.py: fill_holes)."""
+        from ..utils import mesh_clean
+        return mesh_clean.fill_holes(self, method=method, max_edges=max_edges)
+
+    def fill_report(self, method="fan", max_edges=None):
+        """(mesh, FillReport) (utils/mesh_clean.py: fill_report)."""
+        from ..utils import mesh_clean
+        return mesh_clean.fill_report(self, method=method, max_edges=max_edges)
+
     def face_normals(self):
         """Unit face normals [F,3] by the faces' winding; (0,0,0) for a degenerate face."""
         from ..utils import mesh_clean
@@ -334,6 +349,15 @@ class Generator3D(object):
     most N faces but is not the finest such grid, and its topology is not the input's (``Mesh.components()`` reports what it is).
     ``None`` (the default) launches nothing.  The Inferencer does not apply it; generate_obj_mesh_sharded refuses it (VtError).
 
+    ``fill_holes`` / ``fill_holes_max_edges`` (config ``generation.fill_holes`` / ``generation.fill_holes_max_edges``): ``'fan'`` or
+    ``'centroid'`` caps the boundary loops of the finished object mesh -- ``Mesh.fill_holes(method, max_edges)``, utils/mesh_clean.py,
+    csrc/mesh_fill.hip -- after the component filter (a dropped floater's holes are not worth closing) and before ``simplify_nfaces``
+    (which then sees the closed surface), in the same places as those two.  Marching cubes on the unpadded lattice cuts the surface
+    where the object reaches the box: those cuts are planar loops and are capped exactly.  ``fill_holes_max_edges``: only loops of at
+    most that many edges.  It costs three host reads.  With ``with_normals``, ``'fan'`` keeps the marching-cubes normals and values (no
+    vertex is added); ``'centroid'`` is refused in the constructor.  ``None`` (the default) launches nothing.  The Inferencer does not
+    apply it; generate_obj_mesh_sharded refuses it (VtError).
+
     ``with_normals`` (config ``generation.with_normals``; the reference's "whether normals should be estimated"): every route that
     ends in ``extract_mesh`` -- dense, MISE, tactile, the graphed scene -- returns a ``NormalMesh`` whose ``vertex_normals`` and
     ``values`` are those of scikit-image's ``measure.marching_cubes`` (vt_mc_emit_normals: one launch behind the emit, outside the
@@ -360,6 +384,7 @@ class Generator3D(object):
     EXTRACTIONS = ("dense", "mise")
     COMPONENTS = ("all", "largest", "largest_area", "largest_volume")
     REFINE_SAMPLERS = ("device", "numpy")
+    FILL_HOLES = (None, "fan", "centroid")
 
     MAX_SCENE_GRAPHS = 4
     FUSED_CHUNKS_PER_CALL = 256          # attention_local: chunks of points_batch_size points evaluated per launch sequence (see _fused_chunks_per_call)
@@ -370,7 +395,8 @@ class Generator3D(object):
                  resolution0=16, upsampling_steps=3, with_normals=False, padding=0.1, sample=False,
                  input_type=None, vol_info=None, vol_bound=None, simplify_nfaces=None, alpha=0.2,
                  with_img=False, encode_t2d=False, decode_precision="f16x3", depth_origin=None, reference_returns=False,
-                 extraction="dense", components="all", min_component_faces=0, refine_sampler="device"):
+                 extraction="dense", components="all", min_component_faces=0, refine_sampler="device",
+                 fill_holes=None, fill_holes_max_edges=None):
         if isinstance(refinement_step, bool) or not isinstance(refinement_step, numbers.Integral) or refinement_step < 0:
             raise VtError(f"Generator3D: refinement_step must be an integer >= 0 (got {refinement_step!r})")
         if refine_sampler not in self.REFINE_SAMPLERS:
@@ -385,6 +411,18 @@ class Generator3D(object):
         if simplify_nfaces is not None and (isinstance(simplify_nfaces, bool) or not isinstance(simplify_nfaces, numbers.Integral)
                                             or simplify_nfaces < 1):
             raise VtError(f"Generator3D: simplify_nfaces must be a positive integer or None (got {simplify_nfaces!r})")
+        if fill_holes not in self.FILL_HOLES:
+            raise VtError(f"Generator3D: fill_holes must be one of {self.FILL_HOLES} (got {fill_holes!r})")
+        if fill_holes_max_edges is not None and (isinstance(fill_holes_max_edges, bool) or not isinstance(fill_holes_max_edges, numbers.Integral)
+                                                 or fill_holes_max_edges < 3):
+            raise VtError(f"Generator3D: fill_holes_max_edges must be an integer >= 3 or None (got {fill_holes_max_edges!r})")
+        if fill_holes == "centroid" and with_normals:
+            raise VtError("Generator3D(fill_holes='centroid', with_normals=True): the vertices the caps add have no marching-cubes normal or "
+                          "value; use fill_holes='fan', which adds none, or leave with_normals off and take geometric normals of the "
+                          "returned mesh with Mesh.with_vertex_normals()")
+        # None -- the default -- returns the mesh as extracted and launches nothing
+        self.fill_holes = fill_holes
+        self.fill_holes_max_edges = None if fill_holes_max_edges is None else int(fill_holes_max_edges)
         if extraction not in self.EXTRACTIONS:
             raise VtError(f"Generator3D: extraction must be one of {self.EXTRACTIONS} (got {extraction!r})")
         if extraction == "mise" and hasattr(getattr(model, "decoder", None), "fuser"):
@@ -715,9 +753,11 @@ class Generator3D(object):
         return self.components != "all" or self.min_component_faces > 0
 
     def _clean(self, mesh):
-        """The returned components of a finished object mesh (``components``, ``min_component_faces``), then simplified to
-        ``simplify_nfaces`` faces; the mesh itself with the defaults."""
+        """The returned components of a finished object mesh (``components``, ``min_component_faces``), its boundary loops capped
+        (``fill_holes``), then simplified to ``simplify_nfaces`` faces; the mesh itself with the defaults."""
         mesh = self._kept_components(mesh)
+        if self.fill_holes is not None and mesh.faces.shape[0] > 0:
+            mesh = mesh.fill_holes(self.fill_holes, self.fill_holes_max_edges)
         if self.simplify_nfaces is None or mesh.faces.shape[0] <= self.simplify_nfaces:
             return mesh
         from ..utils import mesh_clean
@@ -775,7 +815,7 @@ class Generator3D(object):
         return Mesh(verts, faces)
 
     def generate_obj_mesh_sharded(self, data, group=None):
-        """``_generate_obj_mesh_sharded``; a component filter or ``simplify_nfaces`` is refused before anything is launched."""
+        """``_generate_obj_mesh_sharded``; a component filter, ``fill_holes`` or ``simplify_nfaces`` is refused before anything is launched."""
         self._refuse_refinement("generate_obj_mesh_sharded", "refine the returned mesh with Mesh.refine(generator, c)")
         if self.with_normals:
             raise VtError("generate_obj_mesh_sharded: with_normals is not built for the sharded route; take the normals of the returned "
@@ -783,6 +823,9 @@ class Generator3D(object):
         if self.simplify_nfaces is not None:
             raise VtError("generate_obj_mesh_sharded: simplify_nfaces is not built for the sharded route; simplify the returned mesh with "
                           "Mesh.simplify(nfaces=...)")
+        if self.fill_holes is not None:
+            raise VtError("generate_obj_mesh_sharded: fill_holes is not built for the sharded route; fill the returned mesh with "
+                          "Mesh.fill_holes(method, max_edges)")
         if self._filters_components():
             raise VtError("generate_obj_mesh_sharded: the component filter (components / min_component_faces) is not built for the sharded "
                           "route; filter the returned mesh with Mesh.keep_largest / Mesh.remove_small")

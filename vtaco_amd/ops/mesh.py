@@ -1,6 +1,7 @@
 """Topology of a triangle mesh (vt_mesh_components, vt_mesh_component_table, vt_mesh_component_stats, vt_mesh_edge_stats, vt_mesh_filter:
 csrc/mesh_topo.hip), its normals (vt_mesh_normals: csrc/mesh_normals.hip; ``ops.mesh.normals``) and, at the end of the file, its simplification and welding (vt_mesh_cluster, vt_mesh_weld, vt_mesh_cluster_faces,
-vt_mesh_cluster_place: csrc/mesh_simplify.hip).  A submodule only: callers write ``ops.mesh.components``, ``ops.mesh.component_table``, ``ops.mesh.component_stats``,
+vt_mesh_cluster_place: csrc/mesh_simplify.hip), and behind those its hole filling (vt_mesh_boundary, vt_mesh_boundary_loops, vt_mesh_fill_count,
+vt_mesh_fill_emit: csrc/mesh_fill.hip; ``ops.mesh.boundary_loops``, ``ops.mesh.fill_holes``, which alone take F = 0).  A submodule only: callers write ``ops.mesh.components``, ``ops.mesh.component_table``, ``ops.mesh.component_stats``,
 ``ops.mesh.edge_stats``, ``ops.mesh.filter_components``.  faces are int32 [F,3] and vertices float32 or float64 [V,3] device tensors, as
 ``ops.marching_cubes`` returns them; int64 faces are refused, not converted (a conversion would be a torch computation here: the caller
 writes ``faces.int()``).  F >= 1.  A face index outside [0, V) is found on the device by the calls that read a count back anyway
@@ -280,3 +281,92 @@ def cluster_place(vertices, faces, clusters, n_clusters, placement="quadric"):
                                     PLACEMENTS.index(placement), dev_ptr(out, "out_vertices", out.dtype), dev_ptr(state, "state", I32),
                                     ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "vt_mesh_cluster_place")
     return out
+
+
+# ---- hole filling (csrc/mesh_fill.hip; tests/mesh_fill_ref.py is the definition) ----------------------------------------------------------
+# Half-edge h = 3 f + k runs from faces[f, k] to faces[f, (k+1) % 3]; it is a boundary half-edge when no other half-edge uses its
+# undirected edge.  A loop is a cycle of "the one boundary half-edge that leaves my head", numbered by its smallest half-edge and
+# starting there; boundary half-edges on no cycle (a vertex shared by two holes, a hole beside a flipped face) are irregular.
+BoundaryLoops = namedtuple("BoundaryLoops", ["offsets", "vertices", "half_edges", "n_boundary", "n_irregular"])
+FillResult = namedtuple("FillResult", ["vertices", "faces", "n_loops", "n_filled", "n_new_faces", "n_new_vertices", "n_irregular"])
+FILL_METHODS = ("fan", "centroid")
+
+
+def _fill_faces(what, faces, *others):
+    """``_faces`` that lets F = 0 through."""
+    if torch.is_tensor(faces) and faces.is_cuda and faces.dtype == I32 and tuple(faces.shape) == (0, 3) and all(
+            torch.is_tensor(t) and t.device == faces.device for t in others):
+        return faces
+    return _faces(what, faces, *others)
+
+
+def boundary_loops(faces, n_vertices):
+    """BoundaryLoops(offsets int32 [L+1], vertices, half_edges int32 [n_boundary - n_irregular], n_boundary, n_irregular): loop l owns
+    [offsets[l], offsets[l+1]); its element p is the p-th half-edge after the loop's smallest one and that half-edge's tail vertex
+    (vt_mesh_boundary, vt_mesh_boundary_loops).  Two host reads (n_boundary; L with n_irregular), one for a closed mesh; F = 0 launches
+    nothing.  A face index outside [0, V) raises."""
+    what = "mesh.boundary_loops"
+    faces = _fill_faces(what, faces)
+    V, F, dev = _count(what, n_vertices), faces.shape[0], faces.device
+    none = lambda n: torch.zeros(n, dtype=I32, device=dev)
+    if F == 0:
+        return BoundaryLoops(none(1), none(0), none(0), 0, 0)
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_boundary_workspace_bytes(V, F), dev)
+    nb = ctypes.c_int(0)
+    check(lib.vt_mesh_boundary(dev_ptr(faces, "faces", I32), F, V, ctypes.byref(nb), ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()),
+          "vt_mesh_boundary")
+    NB = nb.value
+    if NB == 0:
+        return BoundaryLoops(none(1), none(0), none(0), 0, 0)
+    off = torch.empty(NB + 1, dtype=I32, device=dev)
+    lv = torch.empty(NB, dtype=I32, device=dev)
+    lh = torch.empty(NB, dtype=I32, device=dev)
+    nl, ni = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.vt_mesh_boundary_loops(dev_ptr(faces, "faces", I32), F, V, NB, dev_ptr(off, "loop_offsets", I32), dev_ptr(lv, "loop_vertices", I32),
+                                     dev_ptr(lh, "loop_half_edges", I32), ctypes.byref(nl), ctypes.byref(ni), ctypes.c_void_p(ws.data_ptr()),
+                                     ws.numel() * 8, stream_ptr()), "vt_mesh_boundary_loops")
+    n = NB - ni.value
+    return BoundaryLoops(off[:nl.value + 1], lv[:n], lh[:n], NB, ni.value)
+
+
+def fill_holes(vertices, faces, method="fan", max_edges=None, loops=None):
+    """FillResult(vertices, faces, n_loops, n_filled, n_new_faces, n_new_vertices, n_irregular): every loop of 3 <= n <= ``max_edges``
+    edges (None: every loop) capped against the direction of its boundary (vt_mesh_fill_count, vt_mesh_fill_emit).  ``'fan'``: faces
+    (v_0, v_{i+1}, v_i), i = 1 .. n-2, no new vertex.  ``'centroid'``: for n >= 4 one new vertex, the loop's mean (an exact sum divided
+    by n in float64, rounded to the vertices' dtype) and faces (c, v_{i+1}, v_i), i = 0 .. n-1; a triangle gets the fan's one face.  New
+    faces follow the originals by (loop, i), new vertices by loop.  A planar loop is capped exactly (the fan of a concave outline folds
+    over itself, with the right signed area); a curved hole gets a crude cap.  ``loops``: ``boundary_loops`` of these faces, when the
+    caller has them.  One more host read (the totals); when nothing is filled the input tensors themselves come back."""
+    what = "mesh.fill_holes"
+    if method not in FILL_METHODS:
+        raise VtError(f"{what}: method must be one of {FILL_METHODS} (got {method!r})")
+    if max_edges is not None and (isinstance(max_edges, bool) or int(max_edges) != max_edges or int(max_edges) < 3):
+        raise VtError(f"{what}: max_edges must be None or an integer >= 3 (got {max_edges!r})")
+    faces = _fill_faces(what, faces, vertices)
+    vertices = _vertices(what, vertices)
+    V, F, dev = vertices.shape[0], faces.shape[0], faces.device
+    if loops is None:
+        loops = boundary_loops(faces, V)
+    L = loops.offsets.shape[0] - 1
+    if L == 0:
+        return FillResult(vertices, faces, 0, 0, 0, 0, loops.n_irregular)
+    off = _i32(what, loops.offsets, L + 1, "loops.offsets")
+    lv = _i32(what, loops.vertices, loops.vertices.shape[0], "loops.vertices")
+    if off.device != dev or lv.device != dev:
+        raise VtError(f"{what}: loops must live on the faces' device")
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_fill_workspace_bytes(L), dev)
+    m = FILL_METHODS.index(method)
+    nfl, nf, nv = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.vt_mesh_fill_count(dev_ptr(off, "loops.offsets", I32), L, m, 0 if max_edges is None else int(max_edges), ctypes.byref(nfl),
+                                 ctypes.byref(nf), ctypes.byref(nv), ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "vt_mesh_fill_count")
+    if nf.value == 0:
+        return FillResult(vertices, faces, L, 0, 0, 0, loops.n_irregular)
+    out_v = torch.empty((V + nv.value, 3), dtype=vertices.dtype, device=dev)
+    out_f = torch.empty((F + nf.value, 3), dtype=I32, device=dev)
+    check(lib.vt_mesh_fill_emit(dev_ptr(vertices, "vertices", vertices.dtype), int(vertices.dtype == F64), V, dev_ptr(faces, "faces", I32), F,
+                                dev_ptr(off, "loops.offsets", I32), dev_ptr(lv, "loops.vertices", I32), L, m, nf.value, nv.value,
+                                dev_ptr(out_v, "out_vertices", out_v.dtype), dev_ptr(out_f, "out_faces", I32), ctypes.c_void_p(ws.data_ptr()),
+                                ws.numel() * 8, stream_ptr()), "vt_mesh_fill_emit")
+    return FillResult(out_v, out_f, L, nfl.value, nf.value, nv.value, loops.n_irregular)

@@ -12,6 +12,9 @@ its meshes in ``trimesh.Trimesh`` (``split``, ``area``, ``volume``, ``is_waterti
     face_normals(mesh) -> [F,3]                  unit, (0,0,0) for a degenerate face (csrc/mesh_normals.hip, as the next two)
     vertex_normals(mesh, weight='area') -> [V,3] 'area' or 'angle'; (0,0,0) for a vertex no live face references
     with_vertex_normals(mesh, weight='area') -> NormalMesh
+    boundary_loops(mesh) -> BoundaryLoops        the boundary half-edges linked into loops (csrc/mesh_fill.hip, as the next two)
+    fill_holes(mesh, method='fan', max_edges=None) -> Mesh       every loop capped; the mesh itself when it has none
+    fill_report(...) -> (Mesh, FillReport)
 
 A mesh is ``generation.Mesh``, any object with ``.vertices`` / ``.faces``, or a ``(vertices, faces)`` pair of device tensors: vertices
 float32 or float64 [V,3], faces int32 [F,3] (int64 faces are converted here).  Components are numbered by their smallest vertex index.
@@ -266,3 +269,62 @@ def with_vertex_normals(mesh, weight="area"):
     from ..conv_onet.generation import NormalMesh
     v, f = _parts(mesh)
     return NormalMesh(v, f, vertex_normals=vertex_normals((v, f), weight=weight), normals_source="geometry")
+
+
+# ---- hole filling (csrc/mesh_fill.hip; tests/mesh_fill_ref.py is the definition) -----------------------------------------------------------
+FillReport = namedtuple("FillReport", ["n_loops", "n_filled", "n_new_faces", "n_new_vertices", "n_boundary", "n_irregular", "loops"])
+FillReport.__doc__ = """n_loops: the boundary loops of the input; n_filled: those that were capped (3 <= edges <= max_edges); n_new_faces,
+n_new_vertices: what the caps added; n_boundary: the input's boundary half-edges; n_irregular: those on no loop (a vertex shared by two
+holes, a hole beside a flipped or non-manifold face), which are never filled; loops: the BoundaryLoops record (offsets, vertices,
+half_edges on the device)."""
+
+
+def boundary_loops(mesh):
+    """``ops.mesh.BoundaryLoops`` of the mesh: loop l owns ``[offsets[l], offsets[l+1])`` of ``vertices`` / ``half_edges``, starts at
+    its smallest half-edge (h = 3 f + k: corner k of face f, to corner (k+1) % 3) and runs with the faces along it; loops are
+    numbered by that half-edge.  Two host reads, one for a closed mesh."""
+    from .. import ops
+    v, f = _parts(mesh)
+    if v.shape[0] == 0:
+        raise VtError("mesh_clean.boundary_loops: a mesh without vertices (V = 0)")
+    return ops.mesh.boundary_loops(f, v.shape[0])
+
+
+def fill_report(mesh, method="fan", max_edges=None):
+    """(Mesh, FillReport).  Every boundary loop of 3 <= n <= ``max_edges`` edges (None: every loop) is capped against the direction of
+    its boundary, so the cap continues the surface's orientation.  ``'fan'``: n - 2 faces about the loop's first vertex, no new vertex.
+    ``'centroid'``: n faces about one new vertex at the loop's mean (a triangle gets its one face).  New faces follow the originals by
+    (loop, position), new vertices by loop; the originals are copied unchanged.  A loop whose vertices lie in one plane -- where
+    marching cubes met the side of its box -- is capped exactly by either method (the fan of a concave outline folds over itself, but
+    its signed area, and so the mesh's volume and winding number, are right); nested planar loops (a hollow cross-section) get two
+    caps of opposite orientation and the result is watertight with the right signed volume.  A curved hole gets a geometrically crude
+    cap: closed and oriented, nothing more.  Irregular boundary edges are counted and left open.  A mesh that has no loop to fill
+    comes back as the same object.  On a ``NormalMesh`` ``'fan'`` keeps ``vertex_normals`` and ``values`` (no vertex is added) and
+    ``'centroid'`` raises.  Three host reads.  Deterministic, bit for bit."""
+    from .. import ops
+    from ..conv_onet.generation import Mesh, NormalMesh
+    what = "mesh_clean.fill_holes"
+    if method not in ops.mesh.FILL_METHODS:
+        raise VtError(f"{what}: method must be one of {ops.mesh.FILL_METHODS} (got {method!r})")
+    if isinstance(mesh, NormalMesh) and method == "centroid":
+        raise VtError(f"{what}: method='centroid' adds vertices that have no marching-cubes normal or value, so it is not applied to a "
+                      "NormalMesh; use method='fan', which adds none, or fill a plain Mesh and take geometric normals with "
+                      "with_vertex_normals()")
+    v, f = _parts(mesh)
+    same = mesh if isinstance(mesh, Mesh) else Mesh(v, f)
+    if f.shape[0] == 0 or v.shape[0] == 0:
+        return same, FillReport(0, 0, 0, 0, 0, 0, None)
+    loops = ops.mesh.boundary_loops(f, v.shape[0])
+    out = ops.mesh.fill_holes(v, f, method=method, max_edges=max_edges, loops=loops)
+    report = FillReport(out.n_loops, out.n_filled, out.n_new_faces, out.n_new_vertices, loops.n_boundary, out.n_irregular, loops)
+    if out.n_new_faces == 0:
+        return same, report
+    if isinstance(mesh, NormalMesh):
+        return NormalMesh(out.vertices, out.faces, vertex_normals=mesh.vertex_normals, values=mesh.values,
+                          normals_source=mesh.normals_source), report
+    return Mesh(out.vertices, out.faces), report
+
+
+def fill_holes(mesh, method="fan", max_edges=None):
+    """``fill_report`` without the report."""
+    return fill_report(mesh, method=method, max_edges=max_edges)[0]
