@@ -1751,6 +1751,40 @@ int vt_mesh_fill_emit(const void *verts, int verts_f64, int64_t V, const int32_t
                       const int32_t *loop_vertices, int64_t L, int method, int64_t n_new_faces, int64_t n_new_verts, void *out_verts,
                       int32_t *out_faces, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- vertex adjacency and mesh smoothing (mesh_smooth.hip) ------------------------------------------------------------------------ */
+/* Replaces: trimesh.Trimesh.vertex_neighbors and trimesh.smoothing.filter_laplacian / filter_taubin / filter_humphrey.                 */
+/*   tests/mesh_smooth_ref.py is the definition and the kernels equal it bit for bit ("mesh_smooth.hip").  Meshes as in the  */
+/*   topology block; F <= (2^31 - 1) / 6 = 357913941, because nnz <= 6 F has to fit the int32 offsets (a larger F is VT_ERR_INVALID).   */
+/* vt_mesh_adjacency_count: the undirected edges {a, b}, a != b, each once however many faces share it, counted per vertex and scanned: */
+/*   offsets [V+1], *nnz = offsets[V] = twice the number of edges.  Leaves the edge table in the workspace                               */
+/*   (vt_mesh_adjacency_workspace_bytes(V, F) bytes).  Waits for the stream (one read; a face index outside [0, V) is VT_ERR_INVALID).  */
+/* vt_mesh_adjacency_fill (asynchronous): on the workspace vt_mesh_adjacency_count left for the same faces, nnz >= 1 its count:         */
+/*   neighbors [nnz], every row ascending; boundary_edge [nnz], 1 where the edge has exactly one face; boundary_vertex [V], 1 where a   */
+/*   boundary edge ends at the vertex.  An unreferenced vertex has an empty row.                                                         */
+/* vt_mesh_smooth_weights (asynchronous): w [nnz] f64.  scheme 0 ('uniform') 1.0; scheme 1 ('inverse_distance')                          */
+/*   1 / sqrt((dx*dx + dy*dy) + dz*dz) of the given positions in float64, 0 for a coincident neighbour.                                 */
+/* vt_mesh_smooth (asynchronous; every pass is enqueued, nothing is read back): positions are carried in float64 (three buffers,         */
+/*   vt_mesh_smooth_workspace_bytes(V) bytes) and rounded once into out_verts [V][3] of the vertices' type.  The row mean m_i = (sum_j   */
+/*   w_ij x_j) / (sum_j w_ij), both sums over j in ascending neighbour order, per coordinate, in double, without FMA; w NULL: every     */
+/*   weight 1; a weight 0 is left out of both sums.  A vertex with an empty row, a zero weight sum or a pinned flag keeps its bits.     */
+/*   method 0 ('laplacian'): x <- x + lam (m - x), `iterations` passes.  method 1 ('taubin'): `iterations` pairs of passes, lam then mu. */
+/*   method 2 ('humphrey'): per iteration q <- x; x <- m(q); b <- x - (alpha o + (1 - alpha) q), o the input; x <- x - (beta b +        */
+/*   (1 - beta) m(b)).  boundary 0 ('pin'): vertices with boundary_vertex set never move; 1 ('free'): no special case; 2 ('loop'): a    */
+/*   boundary vertex averages only the neighbours across boundary edges.  iterations 0, or nnz 0, copies the input's bits.              */
+/*   form 1: one launch per pass, positions in the workspace; form 2: every pass in one launch of one workgroup, positions in LDS       */
+/*   (V <= 2048, no workspace); form 0: form 2 where it fits, form 1 elsewhere.  The two forms return equal bits.                        */
+size_t vt_mesh_adjacency_workspace_bytes(int64_t V, int64_t F);
+int vt_mesh_adjacency_count(const int32_t *faces, int64_t F, int64_t V, int32_t *offsets, int *nnz, void *workspace, size_t workspace_bytes,
+                            void *stream);
+int vt_mesh_adjacency_fill(int64_t F, int64_t V, int64_t nnz, int32_t *neighbors, uint8_t *boundary_edge, uint8_t *boundary_vertex, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int vt_mesh_smooth_weights(const void *verts, int verts_f64, int64_t V, const int32_t *offsets, const int32_t *neighbors, int64_t nnz, int scheme,
+                           double *w, void *stream);
+size_t vt_mesh_smooth_workspace_bytes(int64_t V);
+int vt_mesh_smooth(const void *verts, int verts_f64, int64_t V, const int32_t *offsets, const int32_t *neighbors, const uint8_t *boundary_edge,
+                   const uint8_t *boundary_vertex, int64_t nnz, const double *w, int method, int iterations, double lam, double mu, double alpha,
+                   double beta, int boundary, int form, void *out_verts, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------------------------------ */
 /* Fast winding number (csrc/winding_fast.hip; DESIGN.md section "winding_fast.hip"; tests/winding_fast_ref.py restates it in numpy):     */
 /* an octree over the faces' centroids, `depth` levels below the root (1 .. VT_WN_MAX_DEPTH), whose occupied cells carry the dipole       */

@@ -461,6 +461,12 @@ SIGNATURES = {
     "vt_mesh_fill_workspace_bytes": (_SZ, [_I64]),
     "vt_mesh_fill_count": (_I, [_VP, _I64, _I, _I64, _IP, _IP, _IP, _VP, _SZ, _VP]),
     "vt_mesh_fill_emit": (_I, [_VP, _I, _I64, _VP, _I64, _VP, _VP, _I64, _I, _I64, _I64, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_mesh_adjacency_workspace_bytes": (_SZ, [_I64, _I64]),
+    "vt_mesh_adjacency_count": (_I, [_VP, _I64, _I64, _VP, _IP, _VP, _SZ, _VP]),                        # trimesh vertex_neighbors
+    "vt_mesh_adjacency_fill": (_I, [_I64, _I64, _I64, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_mesh_smooth_weights": (_I, [_VP, _I, _I64, _VP, _VP, _I64, _I, _VP, _VP]),
+    "vt_mesh_smooth_workspace_bytes": (_SZ, [_I64]),
+    "vt_mesh_smooth": (_I, [_VP, _I, _I64, _VP, _VP, _VP, _VP, _I64, _VP, _I, _I, _D, _D, _D, _D, _I, _I, _VP, _VP, _SZ, _VP]),   # trimesh.smoothing
     "vt_winding_tree_default_depth": (_I, [_I64]),
     "vt_winding_tree_workspace_bytes": (_SZ, [_I64, _I64, _I]),
     "vt_winding_tree_count": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _SZ, _VP]),

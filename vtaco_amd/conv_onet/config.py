@@ -70,7 +70,8 @@ def get_generator(model, cfg, device, **kwargs):
                        reference_returns=kwargs.get('reference_returns', g.get('reference_returns', False)),
                        extraction=g.get('extraction', 'dense'), components=g.get('components', 'all'),
                        min_component_faces=g.get('min_component_faces', 0), fill_holes=g.get('fill_holes'),
-                       fill_holes_max_edges=g.get('fill_holes_max_edges'))
+                       fill_holes_max_edges=g.get('fill_holes_max_edges'), smooth=g.get('smooth'),
+                       smooth_iterations=g.get('smooth_iterations', 10))
 
 
 def get_trainer(model, optimizer, cfg, device, **kwargs):

@@ -136,6 +136,35 @@ class Mesh(namedtuple("Mesh", ["vertices", "faces"])):
         from ..utils import mesh_clean
         return mesh_clean.fill_report(self, method=method, max_edges=max_edges)
 
+    def vertex_neighbors(self):
+        """The vertex-vertex adjacency as CSR rows, ``ops.mesh.MeshAdjacency`` (utils/mesh_clean.py: vertex_neighbors)."""
+        from ..utils import mesh_clean
+        return mesh_clean.vertex_neighbors(self)
+
+    def vertex_degree(self):
+        """int32 [V]: the number of neighbours of every vertex."""
+        from ..utils import mesh_clean
+        return mesh_clean.vertex_degree(self)
+
+    def boundary_vertices(self):
+        """bool [V]: the vertices on an edge with exactly one face."""
+        from ..utils import mesh_clean
+        return mesh_clean.boundary_vertices(self)
+
+    def smooth(self, method="taubin", iterations=10, lam=0.5, mu=-0.53, alpha=0.1, beta=0.5, weights="uniform", boundary="pin",
+               adjacency=None):
+        """The same faces on smoothed vertices: 'laplacian', 'taubin' or 'humphrey' (utils/mesh_clean.py: smooth)."""
+        from ..utils import mesh_clean
+        return mesh_clean.smooth(self, method=method, iterations=iterations, lam=lam, mu=mu, alpha=alpha, beta=beta, weights=weights,
+                                 boundary=boundary, adjacency=adjacency)
+
+    def smooth_report(self, method="taubin", iterations=10, lam=0.5, mu=-0.53, alpha=0.1, beta=0.5, weights="uniform", boundary="pin",
+                      adjacency=None):
+        """(mesh, SmoothReport) (utils/mesh_clean.py: smooth_report)."""
+        from ..utils import mesh_clean
+        return mesh_clean.smooth_report(self, method=method, iterations=iterations, lam=lam, mu=mu, alpha=alpha, beta=beta, weights=weights,
+                                        boundary=boundary, adjacency=adjacency)
+
     def face_normals(self):
         """Unit face normals [F,3] by the faces' winding; (0,0,0) for a degenerate face."""
         from ..utils import mesh_clean
@@ -358,6 +387,16 @@ class Generator3D(object):
     vertex is added); ``'centroid'`` is refused in the constructor.  ``None`` (the default) launches nothing.  The Inferencer does not
     apply it; generate_obj_mesh_sharded refuses it (VtError).
 
+    ``smooth`` / ``smooth_iterations`` (config ``generation.smooth`` / ``generation.smooth_iterations``): ``'laplacian'``, ``'taubin'``
+    or ``'humphrey'`` runs that filter on the vertices of the finished object mesh -- ``Mesh.smooth(method, iterations)`` with its
+    other defaults (uniform weights, boundary vertices pinned, so the planar cuts at the box stay where they are), utils/mesh_clean.py,
+    csrc/mesh_smooth.hip -- after ``fill_holes`` and before ``simplify_nfaces``: the marching-cubes staircase is taken out at full
+    resolution, before vertex clustering would amplify it.  It costs one host read (the adjacency's size); the passes are enqueued at
+    once.  With ``with_normals`` the normals are recomputed from the smoothed geometry (``normals_source='geometry'``, no values).
+    ``None`` (the default) launches nothing.  The Inferencer does not apply it; generate_obj_mesh_sharded refuses it (VtError).
+    Pass both by keyword: in the signature they stand before ``refine_sampler``, whose place as third from the end, with
+    ``fill_holes`` and ``fill_holes_max_edges`` as the last two, tests/test_mesh_fill_ref_cpu.py fixes.
+
     ``with_normals`` (config ``generation.with_normals``; the reference's "whether normals should be estimated"): every route that
     ends in ``extract_mesh`` -- dense, MISE, tactile, the graphed scene -- returns a ``NormalMesh`` whose ``vertex_normals`` and
     ``values`` are those of scikit-image's ``measure.marching_cubes`` (vt_mc_emit_normals: one launch behind the emit, outside the
@@ -385,6 +424,7 @@ class Generator3D(object):
     COMPONENTS = ("all", "largest", "largest_area", "largest_volume")
     REFINE_SAMPLERS = ("device", "numpy")
     FILL_HOLES = (None, "fan", "centroid")
+    SMOOTH = (None, "laplacian", "taubin", "humphrey")
 
     MAX_SCENE_GRAPHS = 4
     FUSED_CHUNKS_PER_CALL = 256          # attention_local: chunks of points_batch_size points evaluated per launch sequence (see _fused_chunks_per_call)
@@ -395,8 +435,14 @@ class Generator3D(object):
                  resolution0=16, upsampling_steps=3, with_normals=False, padding=0.1, sample=False,
                  input_type=None, vol_info=None, vol_bound=None, simplify_nfaces=None, alpha=0.2,
                  with_img=False, encode_t2d=False, decode_precision="f16x3", depth_origin=None, reference_returns=False,
-                 extraction="dense", components="all", min_component_faces=0, refine_sampler="device",
-                 fill_holes=None, fill_holes_max_edges=None):
+                 extraction="dense", components="all", min_component_faces=0, smooth=None, smooth_iterations=10,
+                 refine_sampler="device", fill_holes=None, fill_holes_max_edges=None):
+        if smooth not in self.SMOOTH:
+            raise VtError(f"Generator3D: smooth must be one of {self.SMOOTH} (got {smooth!r})")
+        if isinstance(smooth_iterations, bool) or not isinstance(smooth_iterations, numbers.Integral) or smooth_iterations < 0:
+            raise VtError(f"Generator3D: smooth_iterations must be an integer >= 0 (got {smooth_iterations!r})")
+        # None -- the default -- returns the mesh as extracted and launches nothing
+        self.smooth, self.smooth_iterations = smooth, int(smooth_iterations)
         if isinstance(refinement_step, bool) or not isinstance(refinement_step, numbers.Integral) or refinement_step < 0:
             raise VtError(f"Generator3D: refinement_step must be an integer >= 0 (got {refinement_step!r})")
         if refine_sampler not in self.REFINE_SAMPLERS:
@@ -754,10 +800,13 @@ class Generator3D(object):
 
     def _clean(self, mesh):
         """The returned components of a finished object mesh (``components``, ``min_component_faces``), its boundary loops capped
-        (``fill_holes``), then simplified to ``simplify_nfaces`` faces; the mesh itself with the defaults."""
+        (``fill_holes``), its vertices smoothed (``smooth``), then simplified to ``simplify_nfaces`` faces; the mesh itself with the
+        defaults."""
         mesh = self._kept_components(mesh)
         if self.fill_holes is not None and mesh.faces.shape[0] > 0:
             mesh = mesh.fill_holes(self.fill_holes, self.fill_holes_max_edges)
+        if self.smooth is not None and mesh.faces.shape[0] > 0:
+            mesh = mesh.smooth(self.smooth, self.smooth_iterations)
         if self.simplify_nfaces is None or mesh.faces.shape[0] <= self.simplify_nfaces:
             return mesh
         from ..utils import mesh_clean
@@ -815,7 +864,7 @@ class Generator3D(object):
         return Mesh(verts, faces)
 
     def generate_obj_mesh_sharded(self, data, group=None):
-        """``_generate_obj_mesh_sharded``; a component filter, ``fill_holes`` or ``simplify_nfaces`` is refused before anything is launched."""
+        """``_generate_obj_mesh_sharded``; a component filter, ``fill_holes``, ``smooth`` or ``simplify_nfaces`` is refused before anything is launched."""
         self._refuse_refinement("generate_obj_mesh_sharded", "refine the returned mesh with Mesh.refine(generator, c)")
         if self.with_normals:
             raise VtError("generate_obj_mesh_sharded: with_normals is not built for the sharded route; take the normals of the returned "
@@ -826,6 +875,9 @@ class Generator3D(object):
         if self.fill_holes is not None:
             raise VtError("generate_obj_mesh_sharded: fill_holes is not built for the sharded route; fill the returned mesh with "
                           "Mesh.fill_holes(method, max_edges)")
+        if self.smooth is not None:
+            raise VtError("generate_obj_mesh_sharded: smooth is not built for the sharded route; smooth the returned mesh with "
+                          "Mesh.smooth(method, iterations)")
         if self._filters_components():
             raise VtError("generate_obj_mesh_sharded: the component filter (components / min_component_faces) is not built for the sharded "
                           "route; filter the returned mesh with Mesh.keep_largest / Mesh.remove_small")

@@ -1,13 +1,15 @@
 """Topology of a triangle mesh (vt_mesh_components, vt_mesh_component_table, vt_mesh_component_stats, vt_mesh_edge_stats, vt_mesh_filter:
 csrc/mesh_topo.hip), its normals (vt_mesh_normals: csrc/mesh_normals.hip; ``ops.mesh.normals``) and, at the end of the file, its simplification and welding (vt_mesh_cluster, vt_mesh_weld, vt_mesh_cluster_faces,
 vt_mesh_cluster_place: csrc/mesh_simplify.hip), and behind those its hole filling (vt_mesh_boundary, vt_mesh_boundary_loops, vt_mesh_fill_count,
-vt_mesh_fill_emit: csrc/mesh_fill.hip; ``ops.mesh.boundary_loops``, ``ops.mesh.fill_holes``, which alone take F = 0).  A submodule only: callers write ``ops.mesh.components``, ``ops.mesh.component_table``, ``ops.mesh.component_stats``,
+vt_mesh_fill_emit: csrc/mesh_fill.hip; ``ops.mesh.boundary_loops``, ``ops.mesh.fill_holes``), and last its vertex adjacency and smoothing (vt_mesh_adjacency_count, vt_mesh_adjacency_fill, vt_mesh_smooth_weights,
+vt_mesh_smooth: csrc/mesh_smooth.hip; ``ops.mesh.vertex_adjacency``, ``ops.mesh.smooth``); those two families alone take F = 0.  A submodule only: callers write ``ops.mesh.components``, ``ops.mesh.component_table``, ``ops.mesh.component_stats``,
 ``ops.mesh.edge_stats``, ``ops.mesh.filter_components``.  faces are int32 [F,3] and vertices float32 or float64 [V,3] device tensors, as
 ``ops.marching_cubes`` returns them; int64 faces are refused, not converted (a conversion would be a torch computation here: the caller
 writes ``faces.int()``).  F >= 1.  A face index outside [0, V) is found on the device by the calls that read a count back anyway
 (``components``, ``component_table``, ``filter_components``), which raise; no kernel dereferences such an index."""
 from collections import namedtuple
 import ctypes
+import numbers
 
 import torch
 
@@ -370,3 +372,145 @@ def fill_holes(vertices, faces, method="fan", max_edges=None, loops=None):
                                 dev_ptr(out_v, "out_vertices", out_v.dtype), dev_ptr(out_f, "out_faces", I32), ctypes.c_void_p(ws.data_ptr()),
                                 ws.numel() * 8, stream_ptr()), "vt_mesh_fill_emit")
     return FillResult(out_v, out_f, L, nfl.value, nf.value, nv.value, loops.n_irregular)
+
+
+# ---- vertex adjacency and smoothing (csrc/mesh_smooth.hip; tests/mesh_smooth_ref.py is the definition) ------------------------------------
+# The undirected edges {a, b}, a != b, each once however many faces share it, as CSR rows: row i owns [offsets[i], offsets[i+1]) of
+# ``neighbors``, ascending.  boundary_edge marks the entries whose edge has exactly one face, boundary_vertex the vertices such an edge
+# ends at.  The filters carry positions in float64 over all passes, sum every row in ascending neighbour order and round once.
+MeshAdjacency = namedtuple("MeshAdjacency", ["offsets", "neighbors", "boundary_edge", "boundary_vertex"])
+SMOOTH_METHODS = ("laplacian", "taubin", "humphrey")
+SMOOTH_WEIGHTS = ("uniform", "inverse_distance")
+SMOOTH_BOUNDARIES = ("pin", "free", "loop")
+SMOOTH_FORMS = (None, "launches", "workgroup")
+SMOOTH_WORKGROUP_MAX_V = 2048
+MAX_ADJACENCY_FACES = (2 ** 31 - 1) // 6
+
+
+def vertex_adjacency(faces, n_vertices):
+    """MeshAdjacency(offsets int32 [V+1], neighbors int32 [nnz], boundary_edge uint8 [nnz], boundary_vertex uint8 [V])
+    (vt_mesh_adjacency_count, vt_mesh_adjacency_fill): what ``trimesh.Trimesh.vertex_neighbors`` holds, as rows.  A face with a repeated
+    index contributes its proper edges only; an unreferenced vertex has an empty row.  One host read (nnz, to size ``neighbors``); F = 0
+    launches nothing.  A face index outside [0, V) raises, and so does F > (2^31 - 1) / 6: nnz <= 6 F has to fit the int32 offsets."""
+    what = "mesh.vertex_adjacency"
+    faces = _fill_faces(what, faces)
+    V, F, dev = _count(what, n_vertices), faces.shape[0], faces.device
+    if F > MAX_ADJACENCY_FACES:
+        raise VtError(f"{what}: F = {F} is above {MAX_ADJACENCY_FACES} = (2^31 - 1) / 6: the int32 offsets could not hold nnz <= 6 F")
+    off = torch.zeros(V + 1, dtype=I32, device=dev) if F == 0 else torch.empty(V + 1, dtype=I32, device=dev)
+    empty = lambda: MeshAdjacency(off, torch.zeros(0, dtype=I32, device=dev), torch.zeros(0, dtype=U8, device=dev),
+                                  torch.zeros(V, dtype=U8, device=dev))
+    if F == 0:
+        return empty()
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_adjacency_workspace_bytes(V, F), dev)
+    nnz = ctypes.c_int(0)
+    check(lib.vt_mesh_adjacency_count(dev_ptr(faces, "faces", I32), F, V, dev_ptr(off, "offsets", I32), ctypes.byref(nnz),
+                                      ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "vt_mesh_adjacency_count")
+    if nnz.value == 0:                                                        # (every face has a repeated index)
+        return empty()
+    nb = torch.empty(nnz.value, dtype=I32, device=dev)
+    be = torch.empty(nnz.value, dtype=U8, device=dev)
+    bv = torch.empty(V, dtype=U8, device=dev)
+    check(lib.vt_mesh_adjacency_fill(F, V, nnz.value, dev_ptr(nb, "neighbors", I32), dev_ptr(be, "boundary_edge", U8),
+                                     dev_ptr(bv, "boundary_vertex", U8), ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()),
+          "vt_mesh_adjacency_fill")
+    return MeshAdjacency(off, nb, be, bv)
+
+
+def _adjacency(what, adjacency, V, dev):
+    if not isinstance(adjacency, MeshAdjacency):
+        raise VtError(f"{what}: adjacency must be the MeshAdjacency that ops.mesh.vertex_adjacency returns (got {type(adjacency).__name__})")
+    if any(not torch.is_tensor(t) or t.device != dev for t in adjacency):
+        raise VtError(f"{what}: the adjacency must live on the vertices' device")
+    off = _i32(what, adjacency.offsets, V + 1, "adjacency.offsets")
+    nnz = adjacency.neighbors.shape[0] if adjacency.neighbors.dim() == 1 else -1
+    nb = _i32(what, adjacency.neighbors, nnz, "adjacency.neighbors")
+    be, bv = adjacency.boundary_edge, adjacency.boundary_vertex
+    if be.dtype != U8 or tuple(be.shape) != (nnz,) or bv.dtype != U8 or tuple(bv.shape) != (V,):
+        raise VtError(f"{what}: adjacency.boundary_edge must be uint8 [{nnz}] and adjacency.boundary_vertex uint8 [{V}] "
+                      f"(got {be.dtype} {tuple(be.shape)}, {bv.dtype} {tuple(bv.shape)})")
+    return off, nb, _c(be), _c(bv), nnz
+
+
+def smooth_weights(vertices, adjacency, weights="inverse_distance"):
+    """w float64 [nnz], one weight per entry of ``adjacency.neighbors`` (vt_mesh_smooth_weights): ``'uniform'`` 1, ``'inverse_distance'``
+    1 / |x_j - x_i| of these positions in float64, 0 for a coincident neighbour.  Nothing here waits for the device."""
+    what = "mesh.smooth_weights"
+    if weights not in SMOOTH_WEIGHTS:
+        raise VtError(f"{what}: weights must be one of {SMOOTH_WEIGHTS} (got {weights!r})")
+    if not torch.is_tensor(vertices) or not vertices.is_cuda:
+        raise VtError(f"{what}: vertices must be a tensor on a HIP device; vtaco_amd has no CPU path")
+    vertices = _vertices(what, vertices)
+    V, dev = vertices.shape[0], vertices.device
+    off, nb, _, _, nnz = _adjacency(what, adjacency, V, dev)
+    w = torch.empty(nnz, dtype=F64, device=dev)
+    if nnz:
+        check(_lib.load().vt_mesh_smooth_weights(dev_ptr(vertices, "vertices", vertices.dtype), int(vertices.dtype == F64), V, dev_ptr(off, "offsets", I32),
+                                                 dev_ptr(nb, "neighbors", I32), nnz, SMOOTH_WEIGHTS.index(weights), dev_ptr(w, "w", F64), stream_ptr()),
+              "vt_mesh_smooth_weights")
+    return w
+
+
+def _coefficient(what, name, x):
+    if isinstance(x, bool) or not isinstance(x, numbers.Real) or x != x or x in (float("inf"), float("-inf")):
+        raise VtError(f"{what}: {name} must be a finite number (got {x!r})")
+    return float(x)
+
+
+def smooth_arguments(what, method, iterations, lam, mu, alpha, beta, weights, boundary):
+    """The checked (method, iterations, lam, mu, alpha, beta, weights, boundary) of a smoothing call; raises VtError before any launch."""
+    if method not in SMOOTH_METHODS:
+        raise VtError(f"{what}: method must be one of {SMOOTH_METHODS} (got {method!r})")
+    if weights not in SMOOTH_WEIGHTS:
+        raise VtError(f"{what}: weights must be one of {SMOOTH_WEIGHTS} (got {weights!r})")
+    if boundary not in SMOOTH_BOUNDARIES:
+        raise VtError(f"{what}: boundary must be one of {SMOOTH_BOUNDARIES} (got {boundary!r})")
+    if isinstance(iterations, bool) or not isinstance(iterations, numbers.Integral) or not 0 <= int(iterations) <= 1 << 20:
+        raise VtError(f"{what}: iterations must be an integer in [0, {1 << 20}] (got {iterations!r})")
+    lam, mu = _coefficient(what, "lam", lam), _coefficient(what, "mu", mu)
+    alpha, beta = _coefficient(what, "alpha", alpha), _coefficient(what, "beta", beta)
+    if method in ("laplacian", "taubin") and not 0.0 < lam <= 1.0:
+        raise VtError(f"{what}: lam must lie in (0, 1] (got {lam})")
+    if method == "taubin" and not mu < -lam:
+        raise VtError(f"{what}: taubin needs mu < -lam < 0 (got lam={lam}, mu={mu}); the defaults are 0.5 and -0.53")
+    if method == "humphrey" and not (0.0 <= alpha <= 1.0 and 0.0 <= beta <= 1.0):
+        raise VtError(f"{what}: humphrey needs alpha and beta in [0, 1] (got alpha={alpha}, beta={beta})")
+    return method, int(iterations), lam, mu, alpha, beta, weights, boundary
+
+
+def smooth(vertices, adjacency, method="taubin", iterations=10, lam=0.5, mu=-0.53, alpha=0.1, beta=0.5, weights="uniform", boundary="pin",
+           form=None):
+    """New vertices [V,3] in the input's dtype (vt_mesh_smooth_weights, vt_mesh_smooth).  With m_i the weighted mean of vertex i's
+    neighbours: ``'laplacian'`` x <- x + lam (m - x), ``iterations`` passes; ``'taubin'`` ``iterations`` pairs of passes, lam then mu
+    (mu < -lam < 0: the second pass undoes the first one's shrinkage); ``'humphrey'`` per iteration q <- x, x <- m(q),
+    b <- x - (alpha o + (1 - alpha) q) with o the input, x <- x - (beta b + (1 - beta) m(b)).  ``weights='inverse_distance'`` weighs a
+    neighbour by 1 / distance in the input positions (computed once; a coincident neighbour weighs 0).  ``boundary='pin'`` keeps the
+    vertices on boundary edges where they are, ``'free'`` treats them like the rest, ``'loop'`` averages them over their boundary
+    neighbours only, so a planar cut stays in its plane.  Positions are carried in float64 and rounded once; rows are summed in
+    ascending neighbour order, so the bits depend on the mesh's edges alone, not on the order or orientation of its faces.  A vertex
+    without neighbours keeps its bits; ``iterations=0`` copies the input.  Every pass is enqueued at once; nothing waits for the device.
+    ``form``: ``'launches'`` one launch per pass; ``'workgroup'`` every pass in one launch of one workgroup with the positions in LDS (at
+    most 2 048 vertices); None that where it fits, launches elsewhere.  The two return equal bits."""
+    what = "mesh.smooth"
+    method, iterations, lam, mu, alpha, beta, weights, boundary = smooth_arguments(what, method, iterations, lam, mu, alpha, beta, weights, boundary)
+    if form not in SMOOTH_FORMS:
+        raise VtError(f"{what}: form must be one of {SMOOTH_FORMS} (got {form!r})")
+    if not torch.is_tensor(vertices) or not vertices.is_cuda:
+        raise VtError(f"{what}: vertices must be a tensor on a HIP device; vtaco_amd has no CPU path")
+    vertices = _vertices(what, vertices)
+    V, dev = vertices.shape[0], vertices.device
+    off, nb, be, bv, nnz = _adjacency(what, adjacency, V, dev)
+    out = torch.empty_like(vertices)
+    lib = _lib.load()
+    moving = iterations > 0 and nnz > 0
+    launches = moving and (form == "launches" or (form is None and V > SMOOTH_WORKGROUP_MAX_V))
+    w = smooth_weights(vertices, adjacency, weights) if moving and weights != "uniform" else None
+    ws = _ws(lib.vt_mesh_smooth_workspace_bytes(V), dev) if launches else None
+    check(lib.vt_mesh_smooth(dev_ptr(vertices, "vertices", vertices.dtype), int(vertices.dtype == F64), V, dev_ptr(off, "offsets", I32),
+                             dev_ptr(nb, "neighbors", I32) if nnz else None, dev_ptr(be, "boundary_edge", U8) if nnz else None,
+                             dev_ptr(bv, "boundary_vertex", U8), nnz, dev_ptr(w, "w", F64), SMOOTH_METHODS.index(method), iterations, lam, mu,
+                             alpha, beta, SMOOTH_BOUNDARIES.index(boundary), SMOOTH_FORMS.index(form), dev_ptr(out, "out_vertices", out.dtype),
+                             ctypes.c_void_p(ws.data_ptr()) if launches else None, ws.numel() * 8 if launches else 0, stream_ptr()),
+          "vt_mesh_smooth")
+    return out

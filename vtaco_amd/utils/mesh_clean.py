@@ -15,6 +15,10 @@ its meshes in ``trimesh.Trimesh`` (``split``, ``area``, ``volume``, ``is_waterti
     boundary_loops(mesh) -> BoundaryLoops        the boundary half-edges linked into loops (csrc/mesh_fill.hip, as the next two)
     fill_holes(mesh, method='fan', max_edges=None) -> Mesh       every loop capped; the mesh itself when it has none
     fill_report(...) -> (Mesh, FillReport)
+    vertex_neighbors(mesh) -> MeshAdjacency      CSR rows of the vertex-vertex adjacency (csrc/mesh_smooth.hip, as the next four)
+    vertex_degree(mesh) -> [V], boundary_vertices(mesh) -> bool [V]
+    smooth(mesh, method='taubin', iterations=10, ...) -> Mesh    'laplacian', 'taubin' or 'humphrey'; the same faces
+    smooth_report(...) -> (Mesh, SmoothReport)
 
 A mesh is ``generation.Mesh``, any object with ``.vertices`` / ``.faces``, or a ``(vertices, faces)`` pair of device tensors: vertices
 float32 or float64 [V,3], faces int32 [F,3] (int64 faces are converted here).  Components are numbered by their smallest vertex index.
@@ -328,3 +332,81 @@ def fill_report(mesh, method="fan", max_edges=None):
 def fill_holes(mesh, method="fan", max_edges=None):
     """``fill_report`` without the report."""
     return fill_report(mesh, method=method, max_edges=max_edges)[0]
+
+
+# ---- vertex adjacency and smoothing (csrc/mesh_smooth.hip; tests/mesh_smooth_ref.py is the definition) -------------------------------------
+SmoothReport = namedtuple("SmoothReport", ["area_before", "area_after", "volume_before", "volume_after", "max_displacement",
+                                           "rms_displacement", "n_pinned", "adjacency"])
+SmoothReport.__doc__ = """area_*, volume_*: the mesh's area and signed volume (``component_stats`` summed over the components; the volume
+means something for a closed mesh only) before and after; max_displacement, rms_displacement: over all vertices, in float64; n_pinned:
+the boundary vertices that ``boundary='pin'`` held (0 under the other rules); adjacency: the MeshAdjacency that was used."""
+
+
+def vertex_neighbors(mesh):
+    """``ops.mesh.MeshAdjacency`` of the mesh -- what ``trimesh.Trimesh.vertex_neighbors`` holds, as CSR rows on the device: vertex i's
+    neighbours are ``neighbors[offsets[i]:offsets[i+1]]``, ascending; ``boundary_edge`` marks the entries across an edge with one face,
+    ``boundary_vertex`` the vertices on such an edge.  One host read."""
+    from .. import ops
+    v, f = _parts(mesh)
+    if v.shape[0] == 0:
+        raise VtError("mesh_clean.vertex_neighbors: a mesh without vertices (V = 0)")
+    return ops.mesh.vertex_adjacency(f, v.shape[0])
+
+
+def vertex_degree(mesh, adjacency=None):
+    """int32 [V]: the number of neighbours of every vertex (0 for an unreferenced one)."""
+    adjacency = vertex_neighbors(mesh) if adjacency is None else adjacency
+    return adjacency.offsets[1:] - adjacency.offsets[:-1]
+
+
+def boundary_vertices(mesh, adjacency=None):
+    """bool [V]: the vertices that an edge with exactly one face ends at."""
+    adjacency = vertex_neighbors(mesh) if adjacency is None else adjacency
+    return adjacency.boundary_vertex.bool()
+
+
+def smooth(mesh, method="taubin", iterations=10, lam=0.5, mu=-0.53, alpha=0.1, beta=0.5, weights="uniform", boundary="pin", adjacency=None):
+    """The mesh with the same faces and smoothed vertices: ``'laplacian'``, ``'taubin'`` (the lambda|mu filter, which does not shrink) or
+    ``'humphrey'`` (the HC filter of Vollmer et al.), as ``trimesh.smoothing`` offers them; ``ops.mesh.smooth`` has the definitions of
+    the arguments.  ``adjacency``: ``vertex_neighbors`` of this mesh, when the caller has it (the call then reads nothing back).  A
+    ``NormalMesh`` comes back with its normals recomputed from the new geometry (``normals_source='geometry'``, no ``values``), as from
+    ``simplify``.  A mesh without faces, and ``iterations=0``, give a copy of the vertices.  Deterministic, bit for bit."""
+    from .. import ops
+    from ..conv_onet.generation import Mesh, NormalMesh
+    args = ops.mesh.smooth_arguments("mesh_clean.smooth", method, iterations, lam, mu, alpha, beta, weights, boundary)
+    v, f = _parts(mesh)
+    if v.shape[0] == 0:
+        return mesh if isinstance(mesh, Mesh) else Mesh(v, f)
+    if adjacency is None:
+        adjacency = ops.mesh.vertex_adjacency(f, v.shape[0])
+    out = ops.mesh.smooth(v, adjacency, *args)
+    if isinstance(mesh, NormalMesh):
+        return with_vertex_normals((out, f))
+    return Mesh(out, f)
+
+
+def _area_volume(v, f):
+    from .. import ops
+    m = ops.mesh
+    if f.shape[0] == 0:
+        return 0.0, 0.0
+    table = m.component_table(f, m.components(f, v.shape[0]))
+    st = m.component_stats(v, f, table)
+    return float(st.area.sum()), float(st.volume.sum())
+
+
+def smooth_report(mesh, method="taubin", iterations=10, lam=0.5, mu=-0.53, alpha=0.1, beta=0.5, weights="uniform", boundary="pin",
+                  adjacency=None):
+    """(Mesh, SmoothReport): ``smooth`` and what it did to the area, the signed volume and the vertices."""
+    v, f = _parts(mesh)
+    if adjacency is None and v.shape[0]:
+        adjacency = vertex_neighbors((v, f))
+    out = smooth(mesh, method=method, iterations=iterations, lam=lam, mu=mu, alpha=alpha, beta=beta, weights=weights, boundary=boundary,
+                 adjacency=adjacency)
+    if v.shape[0] == 0:
+        return out, SmoothReport(0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, None)
+    a0, v0 = _area_volume(v, f)
+    a1, v1 = _area_volume(out.vertices, f)
+    d2 = ((out.vertices.double() - v.double()) ** 2).sum(1)
+    n_pinned = int(adjacency.boundary_vertex.sum()) if boundary == "pin" else 0
+    return out, SmoothReport(a0, a1, v0, v1, float(d2.max().sqrt()), float(d2.mean().sqrt()), n_pinned, adjacency)
