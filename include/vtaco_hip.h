@@ -1473,10 +1473,14 @@ int vt_chamfer_nn(const float *a, const float *b, int B, int N, int M, float *d_
 /*   beyond).  Outputs per problem: assign [B][n] i32 (person -> object of the padded problem: rows of a, then dummies),        */
 /*   prices [B][n] f32 (the dual prices of the objects), cost_f64 [B] = sum |a_i - b_assign[i]| over the real pairs in float64    */
 /*   (cdist's arithmetic) / N (len(d)), status [B] i32 (0 = converged, 1 = max_rounds Jacobi rounds spent before the last phase  */
-/*   ended: the outputs are not an assignment; the host raises).  Epsilon starts at the cost range / 5, is divided by 5 per phase */
-/*   down to eps_final; the result satisfies eps_final-complementary slackness, so cost <= optimum + n eps_final / N.            */
+/*   ended: the outputs are not an assignment; 2 = a NaN or infinite coordinate, or a cost range beyond f32, found before the    */
+/*   first round: assign is -1, prices 0 and cost_f64 NaN for that problem, the others of the batch are unaffected; the host     */
+/*   raises for both).  Epsilon starts at the cost range / 5 (the cost range is the f32 diagonal of the two clouds' common       */
+/*   bounding box) and is divided by 5 per phase down to eps = eps_final * 2^floor(log2(cost range)) (eps_final itself for a     */
+/*   cost range of 0): relative to the cost range's binade, so clouds scaled by a power of two give the same assignment and      */
+/*   rounds and prices scaled alike.  The result satisfies eps-complementary slackness, so cost <= optimum + n eps / N.          */
 /*   ws: NULL or B * vt_emd_workspace_bytes(N, M) bytes that receive per-problem counters {i64 rounds, i64 bids, i32 phases,   */
-/*   f32 last eps, i64 0}.  vt_emd_workspace_bytes returns 0 for sizes the kernel does not cover.                                */
+/*   f32 last eps (in input units), i64 0}.  vt_emd_workspace_bytes returns 0 for sizes the kernel does not cover.               */
 #define VT_EMD_MAX_POINTS 4096
 #define VT_EMD_WORKSPACE_PER_PROBLEM 32
 size_t vt_emd_workspace_bytes(int n, int m);

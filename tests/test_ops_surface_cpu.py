@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SURFACE = {'EMD_EPS_FINAL': ('const', '1e-06'),
  'EMD_MAX_POINTS': ('const', '4096'),
  'EMD_MAX_ROUNDS': ('const', '500000'),
- 'EmdResult': ('callable', '(emd, assign, prices, rounds, bids, phases)'),
+ 'EmdResult': ('callable', '(emd, assign, prices, rounds, bids, phases, eps)'),
  'FUSION_TENSORS': ('const', "('WK', 'WQ', 'WV', 'trans_conv', 'linear1_w', 'linear1_b', 'linear2_w', 'linear2_b', 'norm2_w', 'norm2_b')"),
  'GRID_SCATTER_SORTED': ('const', 'True'),
  'I32': ('const', 'torch.int32'),

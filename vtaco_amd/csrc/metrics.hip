@@ -167,12 +167,14 @@ emd_auction_kernel(const float *a, int N, const float *b, int M, float eps_final
 
     float lo[3] = {__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()};
     float hi[3] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf()};
+    float finite = 1.f;                                            // 0 once this thread has read a NaN (fminf / fmaxf pass it over)
     for (int j = tid; j < n; j += EMD_THREADS) {
         float x = 0.f, y = 0.f, z = 0.f;
         if (j < M) {
             x = b[3 * j]; y = b[3 * j + 1]; z = b[3 * j + 2];
             lo[0] = fminf(lo[0], x); lo[1] = fminf(lo[1], y); lo[2] = fminf(lo[2], z);
             hi[0] = fmaxf(hi[0], x); hi[1] = fmaxf(hi[1], y); hi[2] = fmaxf(hi[2], z);
+            if (x != x || y != y || z != z) finite = 0.f;
         }
         bx[j] = x; by[j] = y; bz[j] = z;
         price[j] = 0.f;
@@ -182,6 +184,7 @@ emd_auction_kernel(const float *a, int N, const float *b, int M, float eps_final
         for (int k = 0; k < 3; ++k) {
             const float v = a[3 * i + k];
             lo[k] = fminf(lo[k], v); hi[k] = fmaxf(hi[k], v);
+            if (v != v) finite = 0.f;
             if (ax) ax[k * N + i] = v;
         }
     // the cost range: no pair is farther apart than the diagonal of the two clouds' common bounding box
@@ -191,7 +194,30 @@ emd_auction_kernel(const float *a, int N, const float *b, int M, float eps_final
         diag2 += (h - l) * (h - l);
     }
     const float crange = sqrtf(diag2);
-    float eps = fmaxf(crange / EMD_THETA, eps_final);
+    finite = block_min(finite, red);
+    if (!(finite > 0.f) || !(crange < __builtin_huge_valf())) {
+        // A NaN or an infinite coordinate (or finite ones whose range overflows f32): every value of such a bidder would be NaN and
+        // its best column n, one past the arrays.  Status 2 before the first round; uniform over the workgroup (block_min's result).
+        for (int i = tid; i < n; i += EMD_THREADS) {
+            assign_out[(size_t)prob * n + i] = -1;
+            prices_out[(size_t)prob * n + i] = 0.f;
+        }
+        if (tid == 0) {
+            cost_out[prob] = __builtin_nan("");
+            status_out[prob] = 2;
+            if (stats) {
+                EmdStats st;
+                st.rounds = 0; st.bids = 0; st.phases = 0; st.eps_last = 0.f; st.pad = 0;
+                stats[prob] = st;
+            }
+        }
+        return;
+    }
+    // The last epsilon is relative to the cost range's binade, eps_final * 2^floor(log2(crange)): f32 prices grow with the cost range,
+    // and an absolute epsilon below half an ulp of a price no longer raises it (two tied bidders then take one object from each other
+    // for ever).  Powers of two are exact, so clouds scaled by 2^k give the same rounds and assignment, and prices scaled by 2^k.
+    const float eps_end = crange > 0.f ? ldexpf(eps_final, ilogbf(crange)) : eps_final;
+    float eps = fmaxf(crange / EMD_THETA, eps_end);
 
     long long rounds = 0, bids = 0;
     int phases = 0, status = 0;
@@ -261,8 +287,8 @@ emd_auction_kernel(const float *a, int N, const float *b, int M, float eps_final
         }
         if (status) break;
         ++phases;
-        if (eps <= eps_final) break;
-        eps = fmaxf(eps / EMD_THETA, eps_final);
+        if (eps <= eps_end) break;
+        eps = fmaxf(eps / EMD_THETA, eps_end);
         __syncthreads();
     }
     __syncthreads();

@@ -97,9 +97,10 @@ def earth_mover_distance_device(points1, points2, return_assignment=False):
     """``EarthMoverDistance(points1, points2)`` (common.py:45-51: cdist, linear_sum_assignment, sum / len(d)) on the device:
     points1 [N,3], points2 [M,3] (or batches [B,N,3], [B,M,3]) -> the mean matched distance as a float (a float64 array [B] for
     batches).  The assignment is the epsilon-scaling auction of ops.emd_assignment (exact for N != M: the smaller side is padded
-    with zero-cost dummies; cost within max(N, M) * ops.EMD_EPS_FINAL / N of the optimum), its cost is evaluated in float64 as cdist
-    does.  Inputs are taken as float32 and moved to the current HIP device when they are elsewhere.  ``return_assignment``: also
-    the ops.EmdResult (assign [.., max(N, M)] i32: row i of points1 -> row assign[i] of points2, >= M = left unmatched)."""
+    with zero-cost dummies; cost within max(N, M) * eps / N of the optimum, eps = ops.EMD_EPS_FINAL * 2^floor(log2(cost range)),
+    the cost range being the diagonal of the clouds' common bounding box), its cost is evaluated in float64 as cdist does.  A NaN or
+    infinite coordinate raises VtError.  Inputs are taken as float32 and moved to the current HIP device when they are elsewhere.
+    ``return_assignment``: also the ops.EmdResult (assign [.., max(N, M)] i32: row i of points1 -> row assign[i] of points2, >= M = left unmatched)."""
     from . import ops
     from ._lib import VtError
     dev = torch.device("cuda", torch.cuda.current_device())

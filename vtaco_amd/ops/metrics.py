@@ -9,11 +9,12 @@ import torch
 from ._base import _lib, VtError, check, dev_ptr, stream_ptr, I32, _c
 
 
-EMD_EPS_FINAL = 1e-6          # the auction's last epsilon: cost <= optimum + max(N, M) * eps / N, ~4 f32 ulps of a price near 2
+EMD_EPS_FINAL = 1e-6          # the auction's last epsilon at a cost range in [1, 2), ~4 f32 ulps of a price near 2; the kernel ends at
+                              # eps = EMD_EPS_FINAL * 2^floor(log2(cost range)): cost <= optimum + max(N, M) * eps / N
 EMD_MAX_ROUNDS = 500_000      # Jacobi rounds over all phases before the kernel gives up (status 1 -> VtError)
 EMD_MAX_POINTS = 4096         # per side: the padded problem lives in the workgroup's LDS (30 bytes per point)
 
-EmdResult = namedtuple("EmdResult", ["emd", "assign", "prices", "rounds", "bids", "phases"])
+EmdResult = namedtuple("EmdResult", ["emd", "assign", "prices", "rounds", "bids", "phases", "eps"])
 ClosestPoint = namedtuple("ClosestPoint", ["d2", "face", "closest"])
 
 __all__ = ["EMD_EPS_FINAL", "EMD_MAX_ROUNDS", "EMD_MAX_POINTS", "EmdResult", "chamfer_nn", "emd_assignment"]
@@ -52,9 +53,13 @@ def emd_assignment(a, b, eps_final=None, max_rounds=None):
     """Minimum-cost assignment of the rows of a [B,N,3] to the rows of b [B,M,3] under Euclidean cost (scipy's cdist +
     linear_sum_assignment, common.py:45-51) by the epsilon-scaling auction of vt_emd_auction, one workgroup per problem.
     Returns EmdResult(emd [B] f64 on the host: the assignment's cost in float64 / N, assign [B,n] i32 and prices [B,n] f32 on
-    the device (n = max(N, M): person i -> object assign[i] of the problem padded with zero-cost dummies), and the per-problem
-    rounds / bids / phases the auction took).  max(N, M) > EMD_MAX_POINTS, or an auction that spends ``max_rounds`` rounds
-    without finishing, raises VtError."""
+    the device (n = max(N, M): person i -> object assign[i] of the problem padded with zero-cost dummies), the per-problem
+    rounds / bids / phases the auction took, and eps [B] f64: the last epsilon, in the inputs' units).  The cost is within
+    max(N, M) * eps / N of the optimum, with eps = eps_final * 2^floor(log2(cost range)) (``eps_final`` defaults to EMD_EPS_FINAL;
+    the cost range is the f32 diagonal of the two clouds' common bounding box; eps = eps_final when it is 0): the epsilon follows
+    the scale of the clouds, so clouds scaled by a power of two give the same assignment.  max(N, M) > EMD_MAX_POINTS, an auction
+    that spends ``max_rounds`` rounds without finishing, or a NaN or infinite coordinate (found on the device before the first
+    round; "non-finite") raises VtError."""
     a, b = _point_sets(a, b, "emd_assignment")
     B, N, M = a.shape[0], a.shape[1], b.shape[1]
     eps = EMD_EPS_FINAL if eps_final is None else float(eps_final)
@@ -76,12 +81,17 @@ def emd_assignment(a, b, eps_final=None, max_rounds=None):
                              dev_ptr(prices, "prices"), dev_ptr(cost, "cost", torch.float64), dev_ptr(status, "status", I32),
                              ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "vt_emd_auction")
     st, counters = status.cpu(), ws.cpu()
+    bad = torch.nonzero(st == 2).flatten().tolist()
+    if bad:
+        raise VtError(f"emd_assignment: non-finite coordinates, or a coordinate range beyond float32 (problems {bad[:8]}); "
+                      "no auction was run for them")
     bad = torch.nonzero(st).flatten().tolist()
     if bad:
         raise VtError(f"emd_assignment: the auction did not finish within {rounds} rounds (problems {bad[:8]}, "
                       f"eps_final {eps:g}); raise max_rounds or eps_final")
+    eps_last = counters.numpy().view("<f4")[:, 5].astype("float64")          # the record's f32 behind the i32 phases
     return EmdResult(cost.cpu().numpy(), assign, prices, counters[:, 0].numpy(), counters[:, 1].numpy(),
-                     (counters[:, 2] & 0xffffffff).numpy())
+                     (counters[:, 2] & 0xffffffff).numpy(), eps_last)
 
 
 def _cp_status(ws, what):
