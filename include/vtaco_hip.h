@@ -1789,6 +1789,50 @@ int vt_mesh_smooth(const void *verts, int verts_f64, int64_t V, const int32_t *o
                    const uint8_t *boundary_vertex, int64_t nnz, const double *w, int method, int iterations, double lam, double mu, double alpha,
                    double beta, int boundary, int form, void *out_verts, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- mesh subdivision (mesh_subdivide.hip) ----------------------------------------------------------------------------------------- */
+/* Replaces: UpSampleLayer of the reference (src/encoder/manopth/upsample_layer.py: a dict of edges filled face by face on the host)     */
+/*   and trimesh.remesh.subdivide / subdivide_to_size / subdivide_loop.  tests/mesh_subdivide_ref.py is the definition and the kernels   */
+/*   equal it bit for bit ("mesh_subdivide.hip").  Meshes as in the topology block; F = 0 is allowed.  One pipeline: mark a   */
+/*   set of edges, give each marked edge one new vertex V + e, split each face by how many of its edges are marked.                      */
+/* vt_mesh_subdivide_count: mark 0 every edge; mark 1 the edges with (dx*dx + dy*dy) + dz*dz > max_edge^2 in double, d from the lower    */
+/*   index to the higher; mark 2 the edges of the faces with face_mask [F] != 0.  Marked edges are numbered in the order in which a      */
+/*   walk over the half-edges 3 f + k first meets them.  *n_marked; *n_out_faces = sum of 1 + marks(f); *n_irregular = the marked edges  */
+/*   whose direction counts are neither (1, 1) nor (1, 0) / (0, 1).  Leaves table, numbering and face offsets in the workspace           */
+/*   (vt_mesh_subdivide_workspace_bytes(V, F) bytes).  Waits for the stream (one read).  A face with an index outside [0, V) or with a  */
+/*   repeated index makes it VT_ERR_INVALID, and so does V + n_marked >= 2^31; such an index is never dereferenced.                      */
+/* vt_mesh_subdivide_emit (asynchronous): on the workspace vt_mesh_subdivide_count left for the same faces.  out_verts [V + n_marked]    */
+/*   [3] in the vertices' type, out_faces [n_out_faces][3], edge_verts [n_marked][2] = (lo, hi), face_parent [n_out_faces] = the face    */
+/*   every child came from; a face's children are contiguous, faces in their order.  Face (a, b, c) with x on ab, y on bc, z on ca:      */
+/*   3 marks (x,y,z) (a,x,z) (b,y,x) (c,z,y); 0 marks (a,b,c); 1 mark, rotated to the marked edge (p, q), r opposite, m its vertex:      */
+/*   (p,m,r) (m,q,r); 2 marks, rotated to the unmarked edge (p, q), s on qr, t on rp: (r,t,s) and the quad p q s t cut along the         */
+/*   shorter of p-s and q-t (squared lengths in double, s and t the double midpoints of the input positions; a tie: the diagonal at the  */
+/*   lower of the indices p and q): (p,q,s) (p,s,t) or (p,q,t) (q,s,t).  scheme 0 ('midpoint'): originals copied bit for bit, a new      */
+/*   vertex (x_lo + x_hi) * 0.5 in the vertices' type.  scheme 1 ('loop', with mark 0 only; offsets [V+1], neighbors, boundary_edge      */
+/*   [nnz], boundary_vertex [V] from vt_mesh_adjacency_count / _fill), in double, rounded once: a new vertex on a (1, 1) edge            */
+/*   0.375 (x_lo + x_hi) + 0.125 (x_c + x_d), c and d opposite in the lo -> hi and the hi -> lo face, on any other edge the midpoint;   */
+/*   an interior vertex of degree n (1 - n b) x + b sum_j x_j over its row in ascending order, b = 3/16 for n = 3 and 3 / (8 n)          */
+/*   otherwise; a boundary vertex with exactly two boundary neighbours 0.75 x + 0.125 (x_j + x_k); a vertex at an irregular edge, with   */
+/*   another boundary count or with an empty row keeps its bits.                                                                         */
+/* vt_mesh_subdivide_midpoints (asynchronous): the midpoint scheme's vertices for a batch that shares edge_verts [E][2]: out_verts       */
+/*   [B][V + E][3] from verts [B][V][3].  A pair outside [0, V) is not dereferenced; its vertex is NaN.                                  */
+/* vt_mesh_subdivide_bwd (asynchronous): the midpoint scheme's gradient, grad_verts [V][3] from grad_out [V + E][3] of one type:         */
+/*   g_v[i] = g[i] + 0.5 sum of g[V + e] over the edges e at i, every sum exact in two fixed-point limbs against its largest term and    */
+/*   rounded once (vt_mesh_subdivide_bwd_workspace_bytes(V) bytes): equal bits from run to run.  A sum with a term that is not finite    */
+/*   is NaN; a pair outside [0, V) takes no part and sets bit 0 of the workspace's first word.                                           */
+size_t vt_mesh_subdivide_workspace_bytes(int64_t V, int64_t F);
+int vt_mesh_subdivide_count(const void *verts, int verts_f64, int64_t V, const int32_t *faces, int64_t F, int mark, double max_edge,
+                            const uint8_t *face_mask, int *n_marked, int *n_out_faces, int *n_irregular, void *workspace, size_t workspace_bytes,
+                            void *stream);
+int vt_mesh_subdivide_emit(const void *verts, int verts_f64, int64_t V, const int32_t *faces, int64_t F, int64_t n_marked, int64_t n_out_faces,
+                           int scheme, const int32_t *offsets, const int32_t *neighbors, const uint8_t *boundary_edge, const uint8_t *boundary_vertex,
+                           int64_t nnz, void *out_verts, int32_t *out_faces, int32_t *edge_verts, int32_t *face_parent, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int vt_mesh_subdivide_midpoints(const void *verts, int verts_f64, int64_t B, int64_t V, const int32_t *edge_verts, int64_t E, void *out_verts,
+                                void *stream);
+size_t vt_mesh_subdivide_bwd_workspace_bytes(int64_t V);
+int vt_mesh_subdivide_bwd(const int32_t *edge_verts, int64_t V, int64_t E, const void *grad_out, int grad_f64, void *grad_verts, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------------------------------ */
 /* Fast winding number (csrc/winding_fast.hip; DESIGN.md section "winding_fast.hip"; tests/winding_fast_ref.py restates it in numpy):     */
 /* an octree over the faces' centroids, `depth` levels below the root (1 .. VT_WN_MAX_DEPTH), whose occupied cells carry the dipole       */

@@ -467,6 +467,12 @@ SIGNATURES = {
     "vt_mesh_smooth_weights": (_I, [_VP, _I, _I64, _VP, _VP, _I64, _I, _VP, _VP]),
     "vt_mesh_smooth_workspace_bytes": (_SZ, [_I64]),
     "vt_mesh_smooth": (_I, [_VP, _I, _I64, _VP, _VP, _VP, _VP, _I64, _VP, _I, _I, _D, _D, _D, _D, _I, _I, _VP, _VP, _SZ, _VP]),   # trimesh.smoothing
+    "vt_mesh_subdivide_workspace_bytes": (_SZ, [_I64, _I64]),
+    "vt_mesh_subdivide_count": (_I, [_VP, _I, _I64, _VP, _I64, _I, _D, _VP, _IP, _IP, _IP, _VP, _SZ, _VP]),   # UpSampleLayer, trimesh.remesh
+    "vt_mesh_subdivide_emit": (_I, [_VP, _I, _I64, _VP, _I64, _I64, _I64, _I, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_mesh_subdivide_midpoints": (_I, [_VP, _I, _I64, _I64, _VP, _I64, _VP, _VP]),
+    "vt_mesh_subdivide_bwd_workspace_bytes": (_SZ, [_I64]),
+    "vt_mesh_subdivide_bwd": (_I, [_VP, _I64, _I64, _VP, _I, _VP, _VP, _SZ, _VP]),
     "vt_winding_tree_default_depth": (_I, [_I64]),
     "vt_winding_tree_workspace_bytes": (_SZ, [_I64, _I64, _I]),
     "vt_winding_tree_count": (_I, [_VP, _I64, _VP, _I64, _I, _VP, _SZ, _VP]),

@@ -61,17 +61,19 @@ def load_t2d_checkpoint(net, model_file, out_dir, device=None):
 
 def get_generator(model, cfg, device, **kwargs):
     g = cfg['generation']
-    return Generator3D(model, device=device, threshold=cfg['test']['threshold'], resolution0=g['resolution_0'],
-                       upsampling_steps=g['upsampling_steps'], sample=g.get('use_sampling', False),
-                       refinement_step=g.get('refinement_step', 0), refine_sampler=g.get('refine_sampler', 'device'), simplify_nfaces=g.get('simplify_nfaces'),
-                       with_normals=bool(g.get('with_normals', False)),
-                       input_type=cfg['data']['input_type'], padding=cfg['data']['padding'],
-                       with_img=cfg['model'].get('with_img', False), encode_t2d=cfg['model'].get('encoder_t2d', False),
-                       reference_returns=kwargs.get('reference_returns', g.get('reference_returns', False)),
-                       extraction=g.get('extraction', 'dense'), components=g.get('components', 'all'),
-                       min_component_faces=g.get('min_component_faces', 0), fill_holes=g.get('fill_holes'),
-                       fill_holes_max_edges=g.get('fill_holes_max_edges'), smooth=g.get('smooth'),
-                       smooth_iterations=g.get('smooth_iterations', 10))
+    gen = Generator3D(model, device=device, threshold=cfg['test']['threshold'], resolution0=g['resolution_0'],
+                      upsampling_steps=g['upsampling_steps'], sample=g.get('use_sampling', False),
+                      refinement_step=g.get('refinement_step', 0), refine_sampler=g.get('refine_sampler', 'device'), simplify_nfaces=g.get('simplify_nfaces'),
+                      with_normals=bool(g.get('with_normals', False)),
+                      input_type=cfg['data']['input_type'], padding=cfg['data']['padding'],
+                      with_img=cfg['model'].get('with_img', False), encode_t2d=cfg['model'].get('encoder_t2d', False),
+                      reference_returns=kwargs.get('reference_returns', g.get('reference_returns', False)),
+                      extraction=g.get('extraction', 'dense'), components=g.get('components', 'all'),
+                      min_component_faces=g.get('min_component_faces', 0), fill_holes=g.get('fill_holes'),
+                      fill_holes_max_edges=g.get('fill_holes_max_edges'), smooth=g.get('smooth'),
+                      smooth_iterations=g.get('smooth_iterations', 10))
+    # (a method, not a constructor argument: the constructor's parameter list is pinned)
+    return gen.configure_subdivide(g.get('subdivide'), iterations=g.get('subdivide_iterations', 1), max_edge=g.get('subdivide_max_edge'))
 
 
 def get_trainer(model, optimizer, cfg, device, **kwargs):

@@ -165,6 +165,26 @@ class Mesh(namedtuple("Mesh", ["vertices", "faces"])):
         return mesh_clean.smooth_report(self, method=method, iterations=iterations, lam=lam, mu=mu, alpha=alpha, beta=beta, weights=weights,
                                         boundary=boundary, adjacency=adjacency)
 
+    def subdivide(self, iterations=1, face_index=None):
+        """1-to-4 midpoint subdivision, conforming around ``face_index`` (utils/mesh_clean.py: subdivide)."""
+        from ..utils import mesh_clean
+        return mesh_clean.subdivide(self, iterations=iterations, face_index=face_index)
+
+    def subdivide_loop(self, iterations=1):
+        """Loop subdivision (utils/mesh_clean.py: subdivide_loop)."""
+        from ..utils import mesh_clean
+        return mesh_clean.subdivide_loop(self, iterations=iterations)
+
+    def subdivide_to_size(self, max_edge, max_iter=10):
+        """Adaptive midpoint rounds until no edge is longer than ``max_edge`` (utils/mesh_clean.py: subdivide_to_size)."""
+        from ..utils import mesh_clean
+        return mesh_clean.subdivide_to_size(self, max_edge, max_iter=max_iter)
+
+    def subdivide_report(self, scheme="midpoint", iterations=1, face_index=None, max_edge=None, max_iter=10):
+        """(mesh, SubdivideReport) (utils/mesh_clean.py: subdivide_report)."""
+        from ..utils import mesh_clean
+        return mesh_clean.subdivide_report(self, scheme=scheme, iterations=iterations, face_index=face_index, max_edge=max_edge, max_iter=max_iter)
+
     def face_normals(self):
         """Unit face normals [F,3] by the faces' winding; (0,0,0) for a degenerate face."""
         from ..utils import mesh_clean
@@ -418,13 +438,25 @@ class Generator3D(object):
     a negative or non-integer value, and with N > 0 the tactile routes (``with_img``, ``encode_t2d``), the attention decoder, plane
     features, the PointConv baseline and decoder shapes other than hidden 32 / c_dim 32 / 5 blocks (the jet kernel's shape);
     generate_mesh_graphed, generate_obj_mesh_sharded and generate_obj_mesh_tactile refuse N > 0 when called.  The Inferencer ignores
-    it.  ``0`` (the default) launches nothing and returns what it always did."""
+    it.  ``0`` (the default) launches nothing and returns what it always did.
+
+    ``configure_subdivide(scheme, iterations, max_edge)`` (config ``generation.subdivide`` / ``generation.subdivide_iterations`` /
+    ``generation.subdivide_max_edge``; a method, not a constructor argument: tests pin the constructor's parameter list): ``'midpoint'``
+    or ``'loop'`` subdivides the finished object mesh ``iterations`` times, or with ``max_edge`` (``'midpoint'`` only) until no edge is
+    longer -- ``Mesh.subdivide`` / ``subdivide_loop`` / ``subdivide_to_size``, utils/mesh_clean.py, csrc/mesh_subdivide.hip -- after
+    ``smooth`` and before ``simplify_nfaces``, so ``refinement_step`` moves the vertices of the denser mesh onto the isosurface: a
+    coarse extraction, subdivision and refinement reach resolution without a denser lattice.  One host read per round.  With
+    ``with_normals`` the normals are recomputed from the geometry (``normals_source='geometry'``, no values).  ``None`` (the default
+    state) launches nothing.  The Inferencer does not apply it; generate_obj_mesh_sharded refuses it (VtError)."""
 
     EXTRACTIONS = ("dense", "mise")
     COMPONENTS = ("all", "largest", "largest_area", "largest_volume")
     REFINE_SAMPLERS = ("device", "numpy")
     FILL_HOLES = (None, "fan", "centroid")
     SMOOTH = (None, "laplacian", "taubin", "humphrey")
+    SUBDIVIDE = (None, "midpoint", "loop")
+    # configure_subdivide's state; the class attributes are the default: nothing runs
+    subdivide, subdivide_iterations, subdivide_max_edge = None, 1, None
 
     MAX_SCENE_GRAPHS = 4
     FUSED_CHUNKS_PER_CALL = 256          # attention_local: chunks of points_batch_size points evaluated per launch sequence (see _fused_chunks_per_call)
@@ -501,6 +533,30 @@ class Generator3D(object):
             raise VtError("Generator3D: crop / sliding-window mode is not built (no shipped config uses it)")
         if self.refinement_step > 0:
             self._refuse_refinement_config()
+
+    def configure_subdivide(self, scheme=None, iterations=1, max_edge=None):
+        """Subdivide the finished object mesh in ``_clean`` (the class docstring); ``scheme=None`` turns it off again.  Returns self."""
+        if scheme not in self.SUBDIVIDE:
+            raise VtError(f"Generator3D.configure_subdivide: scheme must be one of {self.SUBDIVIDE} (got {scheme!r})")
+        if isinstance(iterations, bool) or not isinstance(iterations, numbers.Integral) or iterations < 0:
+            raise VtError(f"Generator3D.configure_subdivide: iterations must be an integer >= 0 (got {iterations!r})")
+        if max_edge is not None:
+            if isinstance(max_edge, bool) or not isinstance(max_edge, numbers.Real) or not 0.0 < float(max_edge) < float("inf"):
+                raise VtError(f"Generator3D.configure_subdivide: max_edge must be a positive finite number or None (got {max_edge!r})")
+            if scheme != "midpoint":
+                raise VtError(f"Generator3D.configure_subdivide: max_edge goes with scheme='midpoint' (got {scheme!r})")
+        self.subdivide, self.subdivide_iterations = scheme, int(iterations)
+        self.subdivide_max_edge = None if max_edge is None else float(max_edge)
+        return self
+
+    def _subdivided(self, mesh):
+        if self.subdivide is None or mesh.faces.shape[0] == 0:
+            return mesh
+        if self.subdivide_max_edge is not None:
+            return mesh.subdivide_to_size(self.subdivide_max_edge)       # (``iterations`` does not count here)
+        if self.subdivide == "loop":
+            return mesh.subdivide_loop(self.subdivide_iterations)
+        return mesh.subdivide(self.subdivide_iterations)
 
     # -- refinement_step: RMSprop on the vertices against the field's jet -----------
     def _refuse_refinement_config(self):
@@ -800,13 +856,14 @@ class Generator3D(object):
 
     def _clean(self, mesh):
         """The returned components of a finished object mesh (``components``, ``min_component_faces``), its boundary loops capped
-        (``fill_holes``), its vertices smoothed (``smooth``), then simplified to ``simplify_nfaces`` faces; the mesh itself with the
+        (``fill_holes``), its vertices smoothed (``smooth``), its faces subdivided (``configure_subdivide``), then simplified to ``simplify_nfaces`` faces; the mesh itself with the
         defaults."""
         mesh = self._kept_components(mesh)
         if self.fill_holes is not None and mesh.faces.shape[0] > 0:
             mesh = mesh.fill_holes(self.fill_holes, self.fill_holes_max_edges)
         if self.smooth is not None and mesh.faces.shape[0] > 0:
             mesh = mesh.smooth(self.smooth, self.smooth_iterations)
+        mesh = self._subdivided(mesh)
         if self.simplify_nfaces is None or mesh.faces.shape[0] <= self.simplify_nfaces:
             return mesh
         from ..utils import mesh_clean
@@ -878,6 +935,9 @@ class Generator3D(object):
         if self.smooth is not None:
             raise VtError("generate_obj_mesh_sharded: smooth is not built for the sharded route; smooth the returned mesh with "
                           "Mesh.smooth(method, iterations)")
+        if self.subdivide is not None:
+            raise VtError("generate_obj_mesh_sharded: subdivision (configure_subdivide) is not built for the sharded route; subdivide the "
+                          "returned mesh with Mesh.subdivide / subdivide_loop / subdivide_to_size")
         if self._filters_components():
             raise VtError("generate_obj_mesh_sharded: the component filter (components / min_component_faces) is not built for the sharded "
                           "route; filter the returned mesh with Mesh.keep_largest / Mesh.remove_small")

@@ -460,13 +460,14 @@ class Trainer:
         feat = torch.gather(c_img, 1, ids.clamp(max=4).unsqueeze(-1).expand(-1, -1, c_img.shape[2]))
         return feat * (ids != 255).unsqueeze(-1).to(feat.dtype)
 
-    def _hand_metrics(self, data, vf_dict):
+    def _hand_metrics(self, data, vf_dict, hand_upsample=0):
         """{'chamfer_distance', 'hand_joints_error', 'penetration_depth'} of a batch, each the mean over its scenes -- the hand terms of
         the reference's eval_step (training.py:163-166, 393-419): the naive Chamfer of ``points.pc_hand`` against the predicted MANO
         vertices (vt_chamfer_nn), the joint error against the MANO layer on the ground-truth pose, and the penetration depth of the
         predicted hand, moved to the object's frame, into the scene's ground-truth mesh (vt_winding_number_scenes,
         vt_closest_point_mesh_scenes), scaled by max ||pc_ply||.  VTACO_CLOSEST_POINT unset or ``brute``: that launch; ``tree``: a walk
-        of each scene's cached face octree (vt_closest_tree_query: equal bits)."""
+        of each scene's cached face octree (vt_closest_tree_query: equal bits).  ``hand_upsample`` 1 or 2: the penetration depth probes
+        the hand after that many midpoint subdivisions of the MANO faces (``eval.upsample_hand``); 0 launches what it always did."""
         from ..common import hand_in_object_frame
         from ..eval import chamfer_distance_device, hand_joint_error, penetration_depth_scenes
         dev = self.device
@@ -498,19 +499,21 @@ class Trainer:
         depth = penetration_depth_scenes(torch.from_numpy(verts.astype(np.float32)).to(dev),
                                          [self._device_mesh(vf_dict, names[b]) for b in range(B)], scales, winding='fast' if fast else 'exact',
                                          trees=[self._device_tree(vf_dict, names[b]) for b in range(B)] if fast else None, distance=closest,
-                                         ctrees=[self._device_closest_tree(vf_dict, names[b]) for b in range(B)] if closest == "tree" else None)
+                                         ctrees=[self._device_closest_tree(vf_dict, names[b]) for b in range(B)] if closest == "tree" else None,
+                                         hand_upsample=hand_upsample, hand_faces=c_hand.get('mano_faces') if hand_upsample else None)
         return {'chamfer_distance': float(chamfer.double().mean()),
                 'hand_joints_error': float(np.mean(hand_joint_error(joints_gt, joints_pred))),
                 'penetration_depth': float(np.mean(depth))}
 
-    def eval_step(self, data, vf_dict=None, hand_metrics=False):
+    def eval_step(self, data, vf_dict=None, hand_metrics=False, hand_upsample=0):
         """{'loss', 'iou'}: L1 loss on ``points`` and the reference's IoU (compute_iou: both sides cut at the mean ground-truth
         occupancy) on ``points_iou``; with ``with_img`` the query points carry tactile features assigned by the generator's rule
         (the reference's eval_step re-labels its points with libigl winding numbers instead, training.py:105-452: not mirrored).
         A batch with ``'voxels'`` [B,D,D,D] adds 'iou_voxels' (training.py:374-390): the decoder at the voxel centres, cut at
         ``threshold``, against the volume cut at 0.5.
         ``hand_metrics``: adds 'chamfer_distance', 'hand_joints_error' and 'penetration_depth' (training.py:393-419, ``_hand_metrics``);
-        needs a hand encoder, ``vf_dict`` and the batch's points.mano / pc_hand / wrist / name and inputs.pc_ply (VtError otherwise).
+        needs a hand encoder, ``vf_dict`` and the batch's points.mano / pc_hand / wrist / name and inputs.pc_ply (VtError otherwise);
+        ``hand_upsample`` 1 or 2 probes the penetration depth with the subdivided hand (``_hand_metrics``).
         ``train_tactile``: {'loss', 'loss_depth'} of the t2d net (training.py:424-452)."""
         self.model.eval()
         dev = self.device
@@ -518,7 +521,7 @@ class Trainer:
             if self.train_tactile:
                 loss, loss_depth, _ = self.compute_loss_tactile(data)
                 return {'loss': loss.item(), 'loss_depth': loss_depth.item()}
-            hand = self._hand_metrics(data, vf_dict) if hand_metrics else {}
+            hand = self._hand_metrics(data, vf_dict, hand_upsample=hand_upsample) if hand_metrics else {}
             inputs = data.get('inputs').to(dev)
             c = self.model.encode_inputs(inputs)
 
@@ -543,11 +546,11 @@ class Trainer:
             out.update(hand)
         return out
 
-    def evaluate(self, val_loader, vf_dict=None, hand_metrics=False):
+    def evaluate(self, val_loader, vf_dict=None, hand_metrics=False, hand_upsample=0):
         """Mean of eval_step over a loader (``hand_metrics`` with ``vf_dict``: its three hand terms as well)."""
         sums, n = {}, 0
         for batch in val_loader:
-            for k, v in self.eval_step(batch, vf_dict, hand_metrics=hand_metrics).items():
+            for k, v in self.eval_step(batch, vf_dict, hand_metrics=hand_metrics, hand_upsample=hand_upsample).items():
                 sums[k] = sums.get(k, 0.0) + v
             n += 1
         return {k: v / max(n, 1) for k, v in sums.items()}

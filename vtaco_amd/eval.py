@@ -179,26 +179,55 @@ def signed_distance(pts, verts, faces, winding='exact', distance='brute'):
     return torch.where(inside, -dist, dist)
 
 
-def penetration_depth(hand_verts, verts, faces, scale, winding='exact', distance='brute'):
+_HAND_UPSAMPLE = (0, 1, 2)
+_upsample_layer = None
+
+
+def upsample_hand(hand_verts, hand_faces, levels):
+    """The hand's vertices after ``levels`` (0, 1 or 2) midpoint subdivisions of ``hand_faces`` -- the reference's ``UpSampleLayer``
+    (encoder/manopth/upsample_layer.py, csrc/mesh_subdivide.hip): 778 MANO vertices become 3 093, then 12 337, and sample the contact
+    region 4x and 16x as densely.  hand_verts [K,3] or [B,K,3] on the device, hand_faces [Fh,3] int; one connectivity, cached, serves
+    every hand.  ``levels`` 0 returns ``hand_verts`` and launches nothing."""
+    global _upsample_layer
+    if levels not in _HAND_UPSAMPLE or isinstance(levels, bool):
+        raise ValueError(f"hand_upsample must be one of {_HAND_UPSAMPLE} (got {levels!r})")
+    if levels == 0:
+        return hand_verts
+    if hand_faces is None:
+        raise ValueError("hand_upsample > 0 needs hand_faces, the hand's triangles ([Fh,3]; the MANO layer's th_faces)")
+    if _upsample_layer is None:
+        from .encoder.manopth import UpSampleLayer
+        _upsample_layer = UpSampleLayer()
+    v = hand_verts if hand_verts.dim() == 3 else hand_verts.unsqueeze(0)
+    v = v.float().contiguous()
+    f = hand_faces.to(v.device).unsqueeze(0).expand(v.shape[0], -1, -1)
+    for _ in range(levels):
+        v, f = _upsample_layer(v, f)
+    return v if hand_verts.dim() == 3 else v[0]
+
+
+def penetration_depth(hand_verts, verts, faces, scale, winding='exact', distance='brute', hand_upsample=0, hand_faces=None):
     """Penetration depth of a hand into an object mesh as the reference's eval_step measures it (training.py:406-419): 0 when no hand
     vertex has a winding number above 0.5; otherwise the largest distance to the surface (trimesh.proximity.closest_point there,
     vt_closest_point_mesh here) among the vertices that have, times ``scale`` -- the reference passes max ||pc_ply|| of the uncentred
     object cloud.  hand_verts [K,3] in the mesh's frame, verts [V,3] f32, faces [F,3] int on the device -> float.  ``winding``: 'exact'
     (vt_winding_number) or 'fast' (vt_winding_tree_query); ``distance``: 'brute' (vt_closest_point_mesh) or 'tree' (vt_closest_tree_query:
-    equal bits)."""
-    pts = hand_verts.float().contiguous()
+    equal bits).  ``hand_upsample`` 1 or 2 probes the hand after that many midpoint subdivisions of ``hand_faces`` (``upsample_hand``:
+    K + E vertices, 4x and 16x as dense); 0 (the default) probes the K vertices given and launches what it always did."""
+    pts = upsample_hand(hand_verts, hand_faces, hand_upsample).float().contiguous()
     d2 = _distance2(distance, verts, faces, pts)
     return float(_inside_depth(d2, _winding(winding, verts, faces, pts))) * float(scale)
 
 
-def penetration_depth_scenes(hand_verts, meshes, scales, winding='exact', trees=None, distance='brute', ctrees=None):
+def penetration_depth_scenes(hand_verts, meshes, scales, winding='exact', trees=None, distance='brute', ctrees=None, hand_upsample=0,
+                             hand_faces=None):
     """``penetration_depth`` for a batch in one launch sequence each (vt_closest_point_mesh_scenes, vt_winding_number_scenes):
     hand_verts [B,K,3] on the device, meshes = [(verts f32 [V,3], faces i32 [F,3])] per scene, scales [B] -> float64 array [B].
     ``winding='fast'`` queries one tree per scene (``trees``: those of ``ops.winding.build``, built here when not given).
     ``distance='tree'`` walks one face octree per scene (``ctrees``: those of ``ops.metrics.closest_point_tree_build``, built here -- on
-    ``trees`` where given -- when not): equal bits."""
+    ``trees`` where given -- when not): equal bits.  ``hand_upsample`` / ``hand_faces``: as in ``penetration_depth``."""
     from . import ops
-    pts = hand_verts.float().contiguous()
+    pts = upsample_hand(hand_verts, hand_faces, hand_upsample).float().contiguous()
     if distance == 'brute':
         d2 = ops.metrics.closest_point_mesh_scenes(meshes, pts, want_point=False).d2
     elif distance == 'tree':

@@ -2,7 +2,7 @@
 csrc/mesh_topo.hip), its normals (vt_mesh_normals: csrc/mesh_normals.hip; ``ops.mesh.normals``) and, at the end of the file, its simplification and welding (vt_mesh_cluster, vt_mesh_weld, vt_mesh_cluster_faces,
 vt_mesh_cluster_place: csrc/mesh_simplify.hip), and behind those its hole filling (vt_mesh_boundary, vt_mesh_boundary_loops, vt_mesh_fill_count,
 vt_mesh_fill_emit: csrc/mesh_fill.hip; ``ops.mesh.boundary_loops``, ``ops.mesh.fill_holes``), and last its vertex adjacency and smoothing (vt_mesh_adjacency_count, vt_mesh_adjacency_fill, vt_mesh_smooth_weights,
-vt_mesh_smooth: csrc/mesh_smooth.hip; ``ops.mesh.vertex_adjacency``, ``ops.mesh.smooth``); those two families alone take F = 0.  A submodule only: callers write ``ops.mesh.components``, ``ops.mesh.component_table``, ``ops.mesh.component_stats``,
+vt_mesh_smooth: csrc/mesh_smooth.hip; ``ops.mesh.vertex_adjacency``, ``ops.mesh.smooth``), and its subdivision (vt_mesh_subdivide_count, vt_mesh_subdivide_emit, vt_mesh_subdivide_midpoints, vt_mesh_subdivide_bwd: csrc/mesh_subdivide.hip; ``ops.mesh.subdivide``, ``ops.mesh.subdivide_backward``); those three families alone take F = 0.  A submodule only: callers write ``ops.mesh.components``, ``ops.mesh.component_table``, ``ops.mesh.component_stats``,
 ``ops.mesh.edge_stats``, ``ops.mesh.filter_components``.  faces are int32 [F,3] and vertices float32 or float64 [V,3] device tensors, as
 ``ops.marching_cubes`` returns them; int64 faces are refused, not converted (a conversion would be a torch computation here: the caller
 writes ``faces.int()``).  F >= 1.  A face index outside [0, V) is found on the device by the calls that read a count back anyway
@@ -513,4 +513,130 @@ def smooth(vertices, adjacency, method="taubin", iterations=10, lam=0.5, mu=-0.5
                              alpha, beta, SMOOTH_BOUNDARIES.index(boundary), SMOOTH_FORMS.index(form), dev_ptr(out, "out_vertices", out.dtype),
                              ctypes.c_void_p(ws.data_ptr()) if launches else None, ws.numel() * 8 if launches else 0, stream_ptr()),
           "vt_mesh_smooth")
+    return out
+
+
+# ---- subdivision (csrc/mesh_subdivide.hip; tests/mesh_subdivide_ref.py is the definition) ----------------------------------------------------
+# One pipeline: mark a set of edges, give each marked edge one new vertex V + e (e in the order in which a walk over the half-edges first
+# meets the edge: the order of the reference's UpSampleLayer), split each face by how many of its edges are marked.
+SubdivideInfo = namedtuple("SubdivideInfo", ["edge_verts", "face_parent", "n_marked", "n_irregular"])
+SUBDIVIDE_SCHEMES = ("midpoint", "loop")
+
+
+def _subdivide_count(what, vertices, faces, max_edge, face_mask):
+    """The checked arguments and vt_mesh_subdivide_count on them: (vertices, faces, workspace, n_marked, n_out_faces, n_irregular);
+    the workspace is None for F = 0, where nothing is launched."""
+    if max_edge is not None and face_mask is not None:
+        raise VtError(f"{what}: max_edge and face_mask are two marking rules; give one")
+    if max_edge is not None:
+        if isinstance(max_edge, bool) or not isinstance(max_edge, numbers.Real) or not 0.0 < float(max_edge) < float("inf"):
+            raise VtError(f"{what}: max_edge must be a positive finite number (got {max_edge!r})")
+    faces = _fill_faces(what, faces, vertices)
+    vertices = _vertices(what, vertices)
+    V, F, dev = vertices.shape[0], faces.shape[0], faces.device
+    mark = 1 if max_edge is not None else 2 if face_mask is not None else 0
+    if face_mask is not None:
+        if not torch.is_tensor(face_mask) or face_mask.device != dev or face_mask.dtype not in (U8, torch.bool) or tuple(face_mask.shape) != (F,):
+            raise VtError(f"{what}: face_mask must be uint8 or bool [{F}] on the faces' device")
+        face_mask = _c(face_mask.view(U8) if face_mask.dtype == torch.bool else face_mask)
+    if F == 0:
+        return vertices, faces, None, 0, 0, 0
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_subdivide_workspace_bytes(V, F), dev)
+    nm, nf, ni = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.vt_mesh_subdivide_count(dev_ptr(vertices, "vertices", vertices.dtype), int(vertices.dtype == F64), V, dev_ptr(faces, "faces", I32), F,
+                                      mark, float(max_edge) if mark == 1 else 0.0, dev_ptr(face_mask, "face_mask", U8) if mark == 2 else None,
+                                      ctypes.byref(nm), ctypes.byref(nf), ctypes.byref(ni), ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8,
+                                      stream_ptr()), "vt_mesh_subdivide_count")
+    return vertices, faces, ws, nm.value, nf.value, ni.value
+
+
+def subdivide_count(vertices, faces, max_edge=None, face_mask=None):
+    """(n_marked, n_out_faces, n_irregular) of ``subdivide`` with these arguments, and nothing emitted (vt_mesh_subdivide_count).  One
+    host read."""
+    return _subdivide_count("mesh.subdivide_count", vertices, faces, max_edge, face_mask)[3:]
+
+
+def subdivide(vertices, faces, scheme="midpoint", max_edge=None, face_mask=None):
+    """(vertices [V + n_marked, 3] in the input's dtype, faces int32 [F_out, 3], SubdivideInfo(edge_verts int32 [n_marked, 2] = (lo, hi),
+    face_parent int32 [F_out], n_marked, n_irregular)) (vt_mesh_subdivide_count, vt_mesh_subdivide_emit).  Every edge is marked unless
+    ``max_edge`` (the edges longer than it: squared length in float64) or ``face_mask`` (uint8 or bool [F]: the edges of these faces) is
+    given.  A face with 3 marked edges (a, b, c) -> (x,y,z) (a,x,z) (b,y,x) (c,z,y) with x, y, z on ab, bc, ca; 2 and 1 marked edges
+    give 3 and 2 children that keep the orientation and conform with every neighbour; 0 the face itself.  ``'midpoint'``: originals bit
+    for bit, a new vertex (x_lo + x_hi) * 0.5 in the vertices' type.  ``'loop'`` (every edge only): Loop's rules with Warren's weights
+    over ``vertex_adjacency``, in float64 and rounded once; boundary edges and vertices by the curve rule; edges with three faces or a
+    flipped neighbour are counted in n_irregular, take the midpoint, and their ends stay.  One host read (the totals; ``'loop'`` one
+    more for the adjacency).  F = 0, and a rule that marks nothing, return the input tensors themselves.  A face with an index outside
+    [0, V) or with a repeated index raises."""
+    what = "mesh.subdivide"
+    if scheme not in SUBDIVIDE_SCHEMES:
+        raise VtError(f"{what}: scheme must be one of {SUBDIVIDE_SCHEMES} (got {scheme!r})")
+    if scheme == "loop" and (max_edge is not None or face_mask is not None):
+        raise VtError(f"{what}: scheme 'loop' splits every edge; max_edge and face_mask go with 'midpoint'")
+    vertices, faces, ws, E, FO, NI = _subdivide_count(what, vertices, faces, max_edge, face_mask)
+    V, F, dev = vertices.shape[0], faces.shape[0], faces.device
+    if E == 0:
+        return vertices, faces, SubdivideInfo(torch.zeros((0, 2), dtype=I32, device=dev), torch.arange(F, dtype=I32, device=dev), 0, 0)
+    adj = vertex_adjacency(faces, V) if scheme == "loop" else None
+    nnz = adj.neighbors.shape[0] if adj is not None else 0
+    out_v = torch.empty((V + E, 3), dtype=vertices.dtype, device=dev)
+    out_f = torch.empty((FO, 3), dtype=I32, device=dev)
+    ev = torch.empty((E, 2), dtype=I32, device=dev)
+    parent = torch.empty(FO, dtype=I32, device=dev)
+    check(_lib.load().vt_mesh_subdivide_emit(dev_ptr(vertices, "vertices", vertices.dtype), int(vertices.dtype == F64), V, dev_ptr(faces, "faces", I32),
+                                             F, E, FO, SUBDIVIDE_SCHEMES.index(scheme), dev_ptr(adj.offsets, "offsets", I32) if adj else None,
+                                             dev_ptr(adj.neighbors, "neighbors", I32) if nnz else None,
+                                             dev_ptr(adj.boundary_edge, "boundary_edge", U8) if nnz else None,
+                                             dev_ptr(adj.boundary_vertex, "boundary_vertex", U8) if adj else None, nnz,
+                                             dev_ptr(out_v, "out_vertices", out_v.dtype), dev_ptr(out_f, "out_faces", I32),
+                                             dev_ptr(ev, "edge_verts", I32), dev_ptr(parent, "face_parent", I32), ctypes.c_void_p(ws.data_ptr()),
+                                             ws.numel() * 8, stream_ptr()), "vt_mesh_subdivide_emit")
+    return out_v, out_f, SubdivideInfo(ev, parent, E, NI)
+
+
+def _edge_verts(what, edge_verts, dev):
+    if not torch.is_tensor(edge_verts) or edge_verts.device != dev or edge_verts.dtype != I32 or edge_verts.dim() != 2 or edge_verts.shape[1] != 2:
+        raise VtError(f"{what}: edge_verts must be int32 [E,2] on the vertices' device, as SubdivideInfo holds them")
+    return _c(edge_verts)
+
+
+def subdivide_midpoints(vertices, edge_verts):
+    """[B, V + E, 3] from vertices [B, V, 3] (or [V + E, 3] from [V, 3]): the midpoint scheme's vertices on a connectivity that
+    ``subdivide`` made once, for a batch that shares it (vt_mesh_subdivide_midpoints).  Nothing here waits for the device."""
+    what = "mesh.subdivide_midpoints"
+    if not torch.is_tensor(vertices) or not vertices.is_cuda or vertices.dtype not in (torch.float32, F64) or vertices.dim() not in (2, 3) \
+            or vertices.shape[-1] != 3 or vertices.shape[-2] < 1 or vertices.shape[0] < 1:
+        raise VtError(f"{what}: vertices must be a float32 or float64 [B,V,3] or [V,3] tensor on a HIP device")
+    vertices = _c(vertices)
+    edge_verts = _edge_verts(what, edge_verts, vertices.device)
+    V, E = vertices.shape[-2], edge_verts.shape[0]
+    B = vertices.shape[0] if vertices.dim() == 3 else 1
+    out = torch.empty(tuple(vertices.shape[:-2]) + (V + E, 3), dtype=vertices.dtype, device=vertices.device)
+    check(_lib.load().vt_mesh_subdivide_midpoints(dev_ptr(vertices, "vertices", vertices.dtype), int(vertices.dtype == F64), B, V,
+                                                  dev_ptr(edge_verts, "edge_verts", I32) if E else None, E, dev_ptr(out, "out_vertices", out.dtype),
+                                                  stream_ptr()), "vt_mesh_subdivide_midpoints")
+    return out
+
+
+def subdivide_backward(grad_out, edge_verts, n_vertices):
+    """grad_vertices [V,3] (or [B,V,3]) from grad_out [V + E, 3] (or [B, V + E, 3]) of the midpoint scheme: g_v[i] = g[i] + 0.5 sum of
+    g[V + e] over the edges at i (vt_mesh_subdivide_bwd, once per batch item).  Every sum is exact in fixed point and rounded once:
+    equal bits from run to run.  Nothing here waits for the device."""
+    what = "mesh.subdivide_backward"
+    if not torch.is_tensor(grad_out) or not grad_out.is_cuda or grad_out.dtype not in (torch.float32, F64) or grad_out.dim() not in (2, 3) \
+            or grad_out.shape[-1] != 3:
+        raise VtError(f"{what}: grad_out must be a float32 or float64 [B,V+E,3] or [V+E,3] tensor on a HIP device")
+    grad_out = _c(grad_out)
+    edge_verts = _edge_verts(what, edge_verts, grad_out.device)
+    V, E = _count(what, n_vertices), edge_verts.shape[0]
+    if grad_out.shape[-2] != V + E:
+        raise VtError(f"{what}: grad_out must have V + E = {V + E} rows (got {grad_out.shape[-2]})")
+    out = torch.empty(tuple(grad_out.shape[:-2]) + (V, 3), dtype=grad_out.dtype, device=grad_out.device)
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_subdivide_bwd_workspace_bytes(V), grad_out.device)
+    g2, o2 = grad_out.reshape(-1, V + E, 3), out.reshape(-1, V, 3)
+    for b in range(g2.shape[0]):
+        check(lib.vt_mesh_subdivide_bwd(dev_ptr(edge_verts, "edge_verts", I32) if E else None, V, E, dev_ptr(g2[b], "grad_out", g2.dtype),
+                                        int(g2.dtype == F64), dev_ptr(o2[b], "grad_vertices", o2.dtype), ctypes.c_void_p(ws.data_ptr()),
+                                        ws.numel() * 8, stream_ptr()), "vt_mesh_subdivide_bwd")
     return out

@@ -19,6 +19,10 @@ its meshes in ``trimesh.Trimesh`` (``split``, ``area``, ``volume``, ``is_waterti
     vertex_degree(mesh) -> [V], boundary_vertices(mesh) -> bool [V]
     smooth(mesh, method='taubin', iterations=10, ...) -> Mesh    'laplacian', 'taubin' or 'humphrey'; the same faces
     smooth_report(...) -> (Mesh, SmoothReport)
+    subdivide(mesh, iterations=1, face_index=None) -> Mesh       1-to-4 midpoint subdivision (csrc/mesh_subdivide.hip, as the next three)
+    subdivide_loop(mesh, iterations=1) -> Mesh                   Loop's scheme with Warren's weights
+    subdivide_to_size(mesh, max_edge, max_iter=10) -> Mesh       adaptive rounds until no edge is longer than max_edge
+    subdivide_report(...) -> (Mesh, SubdivideReport)
 
 A mesh is ``generation.Mesh``, any object with ``.vertices`` / ``.faces``, or a ``(vertices, faces)`` pair of device tensors: vertices
 float32 or float64 [V,3], faces int32 [F,3] (int64 faces are converted here).  Components are numbered by their smallest vertex index.
@@ -410,3 +414,98 @@ def smooth_report(mesh, method="taubin", iterations=10, lam=0.5, mu=-0.53, alpha
     d2 = ((out.vertices.double() - v.double()) ** 2).sum(1)
     n_pinned = int(adjacency.boundary_vertex.sum()) if boundary == "pin" else 0
     return out, SmoothReport(a0, a1, v0, v1, float(d2.max().sqrt()), float(d2.mean().sqrt()), n_pinned, adjacency)
+
+
+# ---- subdivision (csrc/mesh_subdivide.hip; tests/mesh_subdivide_ref.py is the definition) ---------------------------------------------------
+SubdivideReport = namedtuple("SubdivideReport", ["rounds", "n_vertices", "n_faces", "n_marked", "n_irregular", "face_parent"])
+SubdivideReport.__doc__ = """rounds: the rounds that split something; n_vertices, n_faces, n_marked, n_irregular: one entry per such round
+(the counts after it, the edges it split, the edges among them that are neither interior nor boundary); face_parent int32 [F_out]: the
+face of the INPUT mesh every returned face lies in."""
+
+
+def _positive_count(what, name, x, least=0):
+    if isinstance(x, bool) or int(x) != x or int(x) < least:
+        raise VtError(f"{what}: {name} must be an integer >= {least} (got {x!r})")
+    return int(x)
+
+
+def subdivide_report(mesh, scheme="midpoint", iterations=1, face_index=None, max_edge=None, max_iter=10):
+    """(Mesh, SubdivideReport).  ``max_edge`` None: ``iterations`` rounds of ``scheme`` ('midpoint' or 'loop'), the first over the faces
+    ``face_index`` (int tensor or list of face indices, or a bool / uint8 mask [F]; None: every face) and their neighbours' shared
+    edges, later rounds over the children of those faces.  ``max_edge``: adaptive midpoint rounds, each splitting the edges longer than
+    ``max_edge``, until a round marks nothing; ``VtError`` naming the edges left when ``max_iter`` rounds do not suffice.  One host
+    read per round.  Vertices keep their indices, new ones follow; a ``NormalMesh`` comes back with geometric normals
+    (``normals_source='geometry'``, no values), as after ``smooth``.  A round that marks nothing returns its input."""
+    from .. import ops
+    from ..conv_onet.generation import Mesh, NormalMesh
+    what = "mesh_clean.subdivide"
+    if scheme not in ops.mesh.SUBDIVIDE_SCHEMES:
+        raise VtError(f"{what}: scheme must be one of {ops.mesh.SUBDIVIDE_SCHEMES} (got {scheme!r})")
+    adaptive = max_edge is not None
+    rounds_max = _positive_count(what, "max_iter", max_iter) if adaptive else _positive_count(what, "iterations", iterations)
+    if adaptive and (scheme != "midpoint" or face_index is not None):
+        raise VtError(f"{what}: max_edge goes with scheme='midpoint' and without face_index")
+    if face_index is not None and scheme != "midpoint":
+        raise VtError(f"{what}: face_index goes with scheme='midpoint'")
+    v, f = _parts(mesh)
+    same = mesh if isinstance(mesh, Mesh) else Mesh(v, f)
+    F0 = f.shape[0]
+    if F0 == 0 or v.shape[0] == 0:
+        return same, SubdivideReport(0, [], [], [], [], torch.zeros(0, dtype=torch.int32, device=f.device))
+    mask = None
+    if face_index is not None:
+        idx = torch.as_tensor(face_index, device=f.device)
+        if idx.dtype in (torch.bool, torch.uint8) and tuple(idx.shape) == (F0,):
+            mask = idx.to(torch.uint8)
+        else:
+            idx = idx.reshape(-1).long()
+            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= F0):
+                raise VtError(f"{what}: face_index outside [0, {F0})")
+            mask = torch.zeros(F0, dtype=torch.uint8, device=f.device)
+            mask[idx] = 1
+    parent = torch.arange(F0, dtype=torch.int32, device=f.device)
+    nv, nf, nm, ni = [], [], [], []
+    for it in range(rounds_max + (1 if adaptive else 0)):
+        if adaptive and it == rounds_max:
+            # one more count, nothing emitted: what is left
+            left = ops.mesh.subdivide_count(v, f, max_edge=max_edge)[0]
+            if left:
+                raise VtError(f"mesh_clean.subdivide_to_size: {left} edges are still longer than {max_edge} after {rounds_max} rounds")
+            break
+        ov, of, info = ops.mesh.subdivide(v, f, scheme=scheme, max_edge=max_edge, face_mask=mask)
+        if info.n_marked == 0:
+            break
+        if mask is not None:
+            mask = mask[info.face_parent.long()]                    # the children of the selected faces
+        parent = parent[info.face_parent.long()]
+        v, f = ov, of
+        nv.append(v.shape[0]); nf.append(f.shape[0]); nm.append(info.n_marked); ni.append(info.n_irregular)
+    report = SubdivideReport(len(nm), nv, nf, nm, ni, parent)
+    if not nm:
+        return same, report
+    if isinstance(mesh, NormalMesh):
+        return with_vertex_normals((v, f)), report
+    return Mesh(v, f), report
+
+
+def subdivide(mesh, iterations=1, face_index=None):
+    """1-to-4 midpoint subdivision, ``iterations`` times: every edge gets its midpoint as a new vertex, every face (a, b, c) becomes
+    (x,y,z) (a,x,z) (b,y,x) (c,z,y) -- the reference's ``UpSampleLayer``, and ``trimesh.remesh.subdivide`` up to the numbering of the
+    new vertices.  ``face_index``: only these faces are split in four; their neighbours are split in two or three so that the mesh stays
+    conforming (no T-junction).  ``subdivide_report`` has the rest."""
+    return subdivide_report(mesh, "midpoint", iterations=iterations, face_index=face_index)[0]
+
+
+def subdivide_loop(mesh, iterations=1):
+    """Loop subdivision, ``iterations`` times (``trimesh.remesh.subdivide_loop``): the connectivity of ``subdivide``, old and new
+    vertices placed by Loop's rules with Warren's weights, boundaries by the curve rule (``ops.mesh.subdivide``)."""
+    return subdivide_report(mesh, "loop", iterations=iterations)[0]
+
+
+def subdivide_to_size(mesh, max_edge, max_iter=10):
+    """Adaptive midpoint rounds until no edge is longer than ``max_edge`` (``trimesh.remesh.subdivide_to_size``): each round splits the
+    edges that are too long, a face by how many of its edges are.  ``VtError`` naming the remaining count when ``max_iter`` rounds do
+    not suffice.  One host read per round."""
+    if isinstance(max_edge, bool) or not 0.0 < float(max_edge) < float("inf"):
+        raise VtError(f"mesh_clean.subdivide_to_size: max_edge must be a positive finite number (got {max_edge!r})")
+    return subdivide_report(mesh, "midpoint", max_edge=float(max_edge), max_iter=max_iter)[0]
