@@ -363,6 +363,8 @@ int vt_sample_grid_bwd(int B, int R, int C, const float *pts, int64_t N,
 /* padding, ...) (a point's bin at resolution R - 1 is the cell whose eight corners it touches).  One wave per cell sums its points'    */
 /* contributions in ascending point order and issues its atomics once per cell: the form for clustered query points (the contact        */
 /* clouds of training.py:817-866 put up to 128 points of a scene into a few cells, whose per-point atomics collide).  Same sums.         */
+/* The cells go in eight launches, one per parity of the cell's base node: cells of one parity share no node, so the (up to eight)       */
+/* cell sums that meet at a node are added in a fixed order and the gradient is the same bit for bit in every run.                      */
 int vt_sample_grid_bwd_sorted(int B, int R, int C, const float *pts, int64_t N, double padding, const float *grad_feat,
                               const int *order, const int *seg_lo, const int *seg_hi, float *grad_grid_cl, void *stream);
 /* vt_decode_bwd_contact that leaves d c (the gradient of the sampled features, [B*N][32]) in `grad_c` instead of scattering it:  */

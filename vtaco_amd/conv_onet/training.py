@@ -17,6 +17,7 @@ at model level (``model.decode_img(p, c, c_img)``) or as finger ids (``vt_tactil
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import numpy as np
@@ -30,6 +31,27 @@ from ..eval import compute_iou
 
 # A/B knob: "host" keeps the contact clouds of the VTacO step on the host (numpy, the reference's loop); default: the pixel work on the device
 _DEVICE_CLOUDS = os.environ.get("VTACO_CONTACT_CLOUDS", "device") != "host"
+
+
+class _FingerFeatures(torch.autograd.Function):
+    """Per query row its finger's tactile feature, ``c_img[b, finger[b, s]]``, ONES where ``finger`` is negative (no touch): the
+    forward is torch.gather + torch.where.  The backward sums each finger's rows with a plain reduction, in a fixed order --
+    torch.gather's own backward is a scatter-add with float atomics, and the gradient of every parameter of the tactile encoder
+    then moved in its last bits from one run of a step to the next (tests/test_train_overlap_gpu.py)."""
+
+    @staticmethod
+    def forward(ctx, c_img, finger):
+        feat = torch.gather(c_img, 1, finger.clamp(min=0).unsqueeze(-1).expand(-1, -1, c_img.shape[2]))
+        ctx.save_for_backward(finger)
+        ctx.fingers = c_img.shape[1]
+        return torch.where((finger >= 0).unsqueeze(-1), feat, torch.ones_like(feat))
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        finger, = ctx.saved_tensors
+        zero = dfeat.new_zeros(())
+        # one masked sum over the rows per finger (a row without a touch belongs to none): [B,F,C]
+        return torch.stack([torch.where((finger == f).unsqueeze(-1), dfeat, zero).sum(1) for f in range(ctx.fingers)], dim=1), None
 
 
 class Trainer:
@@ -55,21 +77,24 @@ class Trainer:
         p = data.get('points').to(self.device)
         occ = data.get('points.occ').to(self.device)
         inputs = data.get('inputs').to(self.device)
-        hand = self._hand_branch(inputs, data) if getattr(self.model, 'encoder_hand', None) is not None else None
-        c = self.model.encode_inputs(inputs)
-        logits = self.model.decode(p, c).logits
-        loss = F.l1_loss(logits, occ)
-        if hand is None:
-            zero = logits.new_zeros(())
-            return loss, zero, zero
-        loss_mano, loss_pc = hand()
+        has_hand = getattr(self.model, 'encoder_hand', None) is not None
+        with (self._hand_branch(inputs, data) if has_hand else contextlib.nullcontext()) as hand:
+            c = self.model.encode_inputs(inputs)
+            logits = self.model.decode(p, c).logits
+            loss = F.l1_loss(logits, occ)
+            if hand is None:
+                zero = logits.new_zeros(())
+                return loss, zero, zero
+            loss_mano, loss_pc = hand()
         return loss + loss_mano + loss_pc, loss_mano, loss_pc
 
+    @contextlib.contextmanager
     def _hand_branch(self, inputs, data):
         """The hand branch of a step -- plane PointNet, 2-D U-Net, MANO layer, loss_mano and loss_pc (training.py:476-489) -- queued NOW;
-        returns the function that hands over (loss_mano, loss_pc).  In a single process it runs on a side stream: ~120 small launches
+        yields the function that hands over (loss_mano, loss_pc).  In a single process it runs on a side stream: ~120 small launches
         forward and backward that do not depend on the shape branch and hide under its convolutions (autograd runs a node's backward on
-        its forward's stream)."""
+        its forward's stream).  The caller's stream joins the side stream when the losses are taken, or on the way out of the ``with``
+        block if they never were (an exception in the branch itself or in the caller's own work): no exit leaves it un-joined."""
         dev = self.device
 
         def run():
@@ -78,18 +103,29 @@ class Trainer:
                     F.mse_loss(c_hand['mano_verts'], data.get('points.pc_hand').to(dev).float()))
         side = self._side_stream(1)
         if side is None:
-            return run
+            yield run
+            return
         cur = torch.cuda.current_stream(dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            losses = run()
+        joined = []
 
         def join():
-            cur.wait_stream(side)
-            for t in losses:
-                t.record_stream(cur)
+            if not joined:
+                joined.append(True)
+                cur.wait_stream(side)
+                for t in losses:
+                    t.record_stream(cur)
             return losses
-        return join
+        side.wait_stream(cur)
+        # (made on the caller's stream, read on the side stream forward and backward: the allocator must not hand its block to the
+        # caller's stream while a side-stream reader is still queued)
+        inputs.record_stream(side)
+        try:
+            with torch.cuda.stream(side):
+                losses = run()
+            yield join
+        finally:
+            if not joined:
+                cur.wait_stream(side)
 
     # -- VTacOH: tactile features concatenated to the points near a fingertip (training.py:502-626) -------------------
     def fingertips(self, mano_joints, mano_gt, wrist_euler, pc_ply):
@@ -301,8 +337,8 @@ class Trainer:
             self._sides = (torch.cuda.Stream(device=self.device), torch.cuda.Stream(device=self.device))
         return self._sides[which]
 
-    def _t2d_losses(self, data, s, logits, depth_target, hand=None):
-        loss_mano, loss_pc = (hand or self._hand_branch(s['inputs'], data))()
+    def _t2d_losses(self, data, s, logits, depth_target, hand):
+        loss_mano, loss_pc = hand()
         loss = F.l1_loss(logits, s['occ']) + loss_mano + loss_pc
         if not self.pretrained_t2d:
             loss = loss + F.l1_loss(s['pred_depth'], depth_target) + F.mse_loss(s['digit'], s['cam_info'])
@@ -316,40 +352,44 @@ class Trainer:
         scene's mesh ``vf_dict[name]`` -- vt_winding_number, the exact sum where the reference calls libigl's fast
         approximation.  With ``pretrained_t2d=False`` the depth and digit-pose losses of the t2d net are added (:887-891)."""
         s = self._t2d_samples(data, vf_dict, normalise_depth=False)
-        hand = self._hand_branch(s['inputs'], data)
 
         def tactile():
             c_img = self.model.encode_img_inputs(s['imgs'])                                 # [B,5,C]
-            feat = torch.gather(c_img, 1, s['finger'].clamp(min=0).unsqueeze(-1).expand(-1, -1, c_img.shape[2]))
-            return torch.where((s['finger'] >= 0).unsqueeze(-1), feat, torch.ones_like(feat))    # ones where there is no touch
-        side = self._side_stream()
-        if side is not None:
-            # the tactile feature encoder (Resnet18 over the step's 5 B images: the framework's / MIOpen's kernels) and the shape encoder
-            # (this repository's kernels) do not depend on each other: the first on a side stream, forward AND backward (autograd runs a
-            # node's backward on its forward's stream and orders the streams where gradients cross), joined in front of the decoder
-            cur = torch.cuda.current_stream(self.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
+            return _FingerFeatures.apply(c_img, s['finger'])                                # ones where there is no touch
+        with self._hand_branch(s['inputs'], data) as hand:
+            side = self._side_stream()
+            if side is not None:
+                # the tactile feature encoder (Resnet18 over the step's 5 B images: the framework's / MIOpen's kernels) and the shape encoder
+                # (this repository's kernels) do not depend on each other: the first on a side stream, forward AND backward (autograd runs a
+                # node's backward on its forward's stream and orders the streams where gradients cross), joined in front of the decoder --
+                # also when either encoder raises
+                cur = torch.cuda.current_stream(self.device)
+                side.wait_stream(cur)
+                s['imgs'].record_stream(side)                       # (the caller's tensors the side section reads, as `inputs` above)
+                s['finger'].record_stream(side)
+                try:
+                    with torch.cuda.stream(side):
+                        c_img_all = tactile()
+                    c = self.model.encode_inputs(s['inputs'])
+                finally:
+                    cur.wait_stream(side)
+                c_img_all.record_stream(cur)
+            else:
                 c_img_all = tactile()
-            c = self.model.encode_inputs(s['inputs'])
-            cur.wait_stream(side)
-            c_img_all.record_stream(cur)
-        else:
-            c_img_all = tactile()
-            c = self.model.encode_inputs(s['inputs'])
-        logits = self.model.decode_img(s['p_sample'], c, c_img_all).logits
-        d = s['depths']
-        return self._t2d_losses(data, s, logits, None if self.pretrained_t2d else (d - d.min()) / (d.max() - d.min()), hand)
+                c = self.model.encode_inputs(s['inputs'])
+            logits = self.model.decode_img(s['p_sample'], c, c_img_all).logits
+            d = s['depths']
+            return self._t2d_losses(data, s, logits, None if self.pretrained_t2d else (d - d.min()) / (d.max() - d.min()), hand)
 
     def compute_loss_t2d(self, data, vf_dict):
         """The VTacO step without tactile features (training.py:628-755): the same sample assembly decoded by the plain decoder.
         As in the reference this variant normalises the depth images to [0, 1] BEFORE looking for contact pixels (:643-644), so
         nearly every pixel counts as touched -- reproduced as is."""
         s = self._t2d_samples(data, vf_dict, normalise_depth=True)
-        hand = self._hand_branch(s['inputs'], data)
-        c = self.model.encode_inputs(s['inputs'])
-        logits = self.model.decode(s['p_sample'], c).logits
-        return self._t2d_losses(data, s, logits, s['depths'], hand)
+        with self._hand_branch(s['inputs'], data) as hand:
+            c = self.model.encode_inputs(s['inputs'])
+            logits = self.model.decode(s['p_sample'], c).logits
+            return self._t2d_losses(data, s, logits, s['depths'], hand)
 
     def compute_loss_contact(self, data):
         """(loss, loss_mano, loss_pc, loss_contact) with the decoder's contact head (training.py:896-948): L1 on the occupancy

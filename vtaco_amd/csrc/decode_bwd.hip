@@ -208,8 +208,17 @@ sample_grid_bwd_kernel(DecodeArgs d, const float *grad_feat, float *grad_grid, i
 // normalisations start from the same float32 q = v / divisor + 0.5, and ((2q - 1) + 1) / 2 gives q back exactly, so
 // int(q (R - 1)) IS floor(f) (probed on the CPU over 200 001 coordinates and +-200 ulps around every cell boundary for R = 3, 5, 9,
 // 17, 33: tests/test_decode_train_ref_cpu.py).  It runs only for a caller with segments of its own, e.g. a coarser binning.
+// ORDER OF THE SUM AT A NODE: up to 8 cells share a grid node, and f32 atomics from 8 waves of one launch land in whatever order
+// the waves happen to run -- the grid gradient, and with it every gradient of the shape encoder, then moves in its last bits from
+// one training step to the same step again, and with whatever else the device is running (the hand branch on its side stream).
+// So the cells go in 8 launches, one per parity of the cell's base node (`colour`): two different cells of one parity share no node
+// (they are 2 apart wherever they differ), every node gets at most one atomic per launch, and the launches follow each other in
+// stream order -- the sum at a node is ((((c0 + c1) + c2) + ...) in colour order, bit for bit the same in every run
+// (tests/test_train_overlap_gpu.py holds the whole training step to that).  Segments that are not cells keep the same sum, in the
+// fallback's arbitrary order as before.
 __global__ void __launch_bounds__(256)
-sample_grid_bwd_sorted_kernel(DecodeArgs d, const float *grad_feat, const int *order, const int *seg_lo, const int *seg_hi, float *grad_grid, int C) {
+sample_grid_bwd_sorted_kernel(DecodeArgs d, const float *grad_feat, const int *order, const int *seg_lo, const int *seg_hi, float *grad_grid, int C,
+                              int colour) {
     const int lane = threadIdx.x & 63, ch = (lane & 31) + 32 * blockIdx.y, half = lane >> 5;         // blockIdx.y = the 32-channel slice
     const int R = d.R;
     for (uint32_t g = blockIdx.x * 4 + (threadIdx.x >> 6); g < d.total; g += gridDim.x * 4) {
@@ -220,6 +229,7 @@ sample_grid_bwd_sorted_kernel(DecodeArgs d, const float *grad_feat, const int *o
         float px, py, pz;
         point_of(d, g, t, px, py, pz);
         const Tri head = tri_setup(px, py, pz, d.divisor, R);
+        if ((((head.z0 & 1) << 2) | ((head.y0 & 1) << 1) | (head.x0 & 1)) != colour) continue;      // another launch's cell
         float acc[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] = 0.0f;
@@ -484,7 +494,8 @@ int vt_sample_grid_bwd_sorted(int B, int R, int C, const float *pts, int64_t N, 
     int64_t blocks = ((int64_t)d.total + 3) / 4;
     const int64_t cap = 32 * vt_num_cus();
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(sample_grid_bwd_sorted_kernel, dim3((unsigned)blocks, (unsigned)(C / 32)), dim3(256), 0, (hipStream_t)stream, d, grad_feat, order, seg_lo, seg_hi, grad_grid_cl, C);
+    for (int colour = 0; colour < 8; ++colour)                      // one launch per cell parity: a fixed order of the sum at every node
+        hipLaunchKernelGGL(sample_grid_bwd_sorted_kernel, dim3((unsigned)blocks, (unsigned)(C / 32)), dim3(256), 0, (hipStream_t)stream, d, grad_feat, order, seg_lo, seg_hi, grad_grid_cl, C, colour);
     return vt_check(hipGetLastError(), "vt_sample_grid_bwd_sorted");
 }
 

@@ -94,7 +94,8 @@ GRID_SCATTER_SORTED = os.environ.get("VTACO_GRID_SCATTER", "sorted") != "points"
 
 def sample_grid_bwd_sorted_into(ggrid_cl, pts, grad_feat, padding=0.1):
     """Scatter d feat [B,N,C] of query points pts [B,N,3] into the zeroed channels-last grid gradient [B,R,R,R,C], the points grouped
-    by trilinear cell (vt_voxel_build at resolution R - 1 + vt_sample_grid_bwd_sorted)."""
+    by trilinear cell (vt_voxel_build at resolution R - 1 + vt_sample_grid_bwd_sorted: the cell sums that meet at a node are added in
+    a fixed order, so the result is reproducible bit for bit)."""
     B, R, C = ggrid_cl.shape[0], ggrid_cl.shape[1], ggrid_cl.shape[4]
     N = pts.shape[1]
     if B * N == 0:                                                  # no points: the zeroed gradient is the answer
