@@ -87,6 +87,30 @@ def test_fill_holes(name, method):
             assert bool(comps.watertight.all()) and bool(comps.oriented.all()), tag
 
 
+def test_more_than_256_scan_blocks():
+    """87 382 disjoint triangles: the 3 F flags, and the NB = 262 146 boundary half-edges after them, each take 257 blocks of the scan, so
+    the one workgroup that scans the block sums goes round its loop twice and carries a sum over -- in the int32 scan of the flags and in
+    the 64-bit scan of the loop heads.  Every triangle is a loop of 3 and gets one face."""
+    from vtaco_amd import ops
+    n = 87382
+    f = np.arange(3 * n, dtype=np.int32).reshape(n, 3)
+    v = (np.arange(9 * n) % 97).astype(np.float32).reshape(3 * n, 3)
+    assert -(-3 * n // 1024) == 257
+    ref = R.fill_holes(v, f, "fan")
+    loops = ref["loops"]
+    assert (loops["n_loops"], loops["n_boundary"], loops["n_irregular"], ref["n_new_faces"]) == (n, 3 * n, 0, n)
+    tv, tf = _dev(v, f)
+    got, again = ops.mesh.boundary_loops(tf, 3 * n), ops.mesh.boundary_loops(tf, 3 * n)
+    for k in ("offsets", "vertices", "half_edges"):
+        assert np.array_equal(getattr(got, k).cpu().numpy(), loops[k]) and torch.equal(getattr(got, k), getattr(again, k)), k
+    assert (got.n_boundary, got.n_irregular) == (3 * n, 0) == (again.n_boundary, again.n_irregular)
+    got, again = ops.mesh.fill_holes(tv, tf, method="fan"), ops.mesh.fill_holes(tv, tf, method="fan")
+    for k in COUNTS:
+        assert getattr(got, k) == ref[k] == getattr(again, k), k
+    assert np.array_equal(got.faces.cpu().numpy(), ref["faces"]) and torch.equal(got.faces, again.faces)
+    assert got.vertices.cpu().numpy().tobytes() == v.tobytes() == again.vertices.cpu().numpy().tobytes()
+
+
 def test_max_edges_and_report():
     from vtaco_amd.conv_onet.generation import Mesh
     from vtaco_amd.utils import mesh_clean

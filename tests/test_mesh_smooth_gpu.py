@@ -103,6 +103,26 @@ def test_fixture(name):
                     assert _bits(got[5:]) == _bits(x[5:])                  # every weight 0: the vertex stays
 
 
+@pytest.mark.parametrize("V", [1022, 1023, 1024])
+def test_offsets_at_the_scan_chunk(V):
+    """The scan that writes offsets, in the caller's array and in the workspace, runs over V + 1 = 1023, 1024 and 1025 elements: below, on
+    and above its 1 024-element chunk.  The strip has 1 004 vertices; the ones past it are unreferenced and their rows are empty."""
+    v, f = R.T.grid_strip(1000)
+    assert v.shape[0] == 1004
+    got, ref = _adjacency(f, V)
+    assert got.offsets.numel() == V + 1 and int(got.offsets[-1]) == ref["neighbors"].shape[0]
+
+
+def test_more_than_256_scan_blocks():
+    """87 382 disjoint triangles: the V + 1 = 262 147 offsets take 257 blocks of the scan, so the one workgroup that scans the block sums
+    goes round its loop twice and carries a sum over."""
+    n = 87382
+    f = np.arange(3 * n, dtype=np.int32).reshape(n, 3)
+    assert -(-(3 * n + 1) // 1024) == 257
+    got, ref = _adjacency(f, 3 * n)
+    assert got.neighbors.numel() == ref["neighbors"].shape[0] == 524292
+
+
 def test_weights_are_the_definitions(spheres):
     from vtaco_amd import ops
     cases = [(n,) + R.fixture(n) for n in ("coincident", "fan300", "odd")] + [("cut",) + spheres["cut"][:2]]

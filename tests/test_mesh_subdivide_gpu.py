@@ -98,6 +98,17 @@ def test_chunk_fixtures_sit_on_the_scan_chunk():
     assert [3 * R.fixture(n)[1].shape[0] - k * R.MT_CHUNK for n, k in (("chunk_below", 1), ("chunk_at", 3), ("chunk_above", 2))] == [-1, 0, 1]
 
 
+def test_more_than_256_scan_blocks():
+    """87 382 disjoint triangles: the 3 F = 262 146 first-use flags take 257 blocks of the scan, so the one workgroup that scans the block
+    sums goes round its loop twice and carries a sum over.  Every edge is marked: 4 F faces."""
+    n = 87382
+    f = np.arange(3 * n, dtype=np.int32).reshape(n, 3)
+    v = (np.arange(9 * n) % 97).astype(np.float32).reshape(3 * n, 3)
+    assert -(-3 * n // R.MT_CHUNK) == 257
+    info = _check(v, f)
+    assert info["n_marked"] == 3 * n and info["face_parent"].shape[0] == 349528
+
+
 def test_loop_leaves_the_ends_of_irregular_edges_in_place():
     from vtaco_amd import ops
     v, f = R.fixture("odd")

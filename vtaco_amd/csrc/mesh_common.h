@@ -1,9 +1,13 @@
-// What mesh_topo.hip and mesh_simplify.hip share: the launch constants, faces through LDS, the exclusive prefix scan of a predicate, the
-// per-(wave, key) combination in front of an atomic, the order-preserving integer image of a double and the two-limb fixed-point sums.
+// What the mesh and octree kernel files share (DESIGN.md, section "mesh_common.h and mesh_edges.h"): the launch constants, faces through
+// LDS, the exclusive prefix scan of int32 or 64-bit values, the per-(wave, key) combination in front of an atomic, the order-preserving
+// integer image of a double, the two-limb fixed-point sums, and the host's word copy and status read.  The edge table is in mesh_edges.h.
 // Everything lives in an unnamed namespace: each translation unit has its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <cstddef>
+#include <type_traits>
 
 #include "vt_common.h"
 
@@ -41,13 +45,16 @@ __device__ inline bool load_face(const int32_t *faces, int F, int V, int32_t *ld
     return in;
 }
 
-// ---- exclusive prefix scan of a predicate over [0, n) ---------------------------------------------------------------------------------
-__device__ inline int block_inclusive_scan(int x, int *lds) {
+// ---- exclusive prefix scan of fn(i) over [0, n) -----------------------------------------------------------------------------------------
+// S is the summed type, int32_t or u64 (two 32-bit fields scanned at once), taken from the pointers; fn returns the value, and a
+// predicate's bool counts as 0 or 1.
+template <class S>
+__device__ inline S block_inclusive_scan(S x, S *lds) {
     __syncthreads();
     lds[threadIdx.x] = x;
     __syncthreads();
     for (int d = 1; d < MT_THREADS; d <<= 1) {
-        const int y = (int)threadIdx.x >= d ? lds[threadIdx.x - d] : 0;
+        const S y = (int)threadIdx.x >= d ? lds[threadIdx.x - d] : 0;
         __syncthreads();
         lds[threadIdx.x] += y;
         __syncthreads();
@@ -55,57 +62,64 @@ __device__ inline int block_inclusive_scan(int x, int *lds) {
     return lds[threadIdx.x];
 }
 
-template <class P>
-__global__ void __launch_bounds__(MT_THREADS) scan_count_kernel(P pred, int64_t n, int32_t *bsum) {
-    __shared__ int lds[MT_THREADS];
+template <class Fn, class S>
+__global__ void __launch_bounds__(MT_THREADS) scan_count_kernel(Fn fn, int64_t n, S *bsum) {
+    __shared__ S lds[MT_THREADS];
     const int64_t i0 = (int64_t)blockIdx.x * MT_CHUNK + (int64_t)threadIdx.x * MT_ITEMS;
-    int s = 0;
+    S s = 0;
 #pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) s += (i0 + k < n && pred(i0 + k)) ? 1 : 0;
-    const int incl = block_inclusive_scan(s, lds);
+    for (int k = 0; k < MT_ITEMS; ++k) s += i0 + k < n ? (S)fn(i0 + k) : 0;
+    const S incl = block_inclusive_scan(s, lds);
     if (threadIdx.x == MT_THREADS - 1) bsum[blockIdx.x] = incl;
 }
 
 // one workgroup: bsum[0..nb) becomes its exclusive scan, *total the sum
-__global__ void __launch_bounds__(MT_THREADS) scan_blocks_kernel(int32_t *bsum, int nb, int32_t *total) {
-    __shared__ int lds[MT_THREADS];
-    int carry = 0;
+template <class S>
+__global__ void __launch_bounds__(MT_THREADS) scan_blocks_kernel(S *bsum, int nb, S *total) {
+    __shared__ S lds[MT_THREADS];
+    S carry = 0;
     for (int base = 0; base < nb; base += MT_THREADS) {
         const int i = base + (int)threadIdx.x;
-        const int x = i < nb ? bsum[i] : 0;
-        const int incl = block_inclusive_scan(x, lds);
+        const S x = i < nb ? bsum[i] : 0;
+        const S incl = block_inclusive_scan(x, lds);
         if (i < nb) bsum[i] = carry + incl - x;
         carry += lds[MT_THREADS - 1];
     }
     if (threadIdx.x == 0) *total = carry;
 }
 
-template <class P>
-__global__ void __launch_bounds__(MT_THREADS) scan_write_kernel(P pred, int64_t n, const int32_t *bsum, int32_t *pos) {
-    __shared__ int lds[MT_THREADS];
+template <class Fn, class S, class Copy>
+__global__ void __launch_bounds__(MT_THREADS) scan_write_kernel(Fn fn, int64_t n, const S *bsum, S *out, Copy copy) {
+    __shared__ S lds[MT_THREADS];
     const int64_t i0 = (int64_t)blockIdx.x * MT_CHUNK + (int64_t)threadIdx.x * MT_ITEMS;
-    int fl[MT_ITEMS];
-    int s = 0;
+    S x[MT_ITEMS];
+    S s = 0;
 #pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) { fl[k] = (i0 + k < n && pred(i0 + k)) ? 1 : 0; s += fl[k]; }
-    int at = bsum[blockIdx.x] + block_inclusive_scan(s, lds) - s;
+    for (int k = 0; k < MT_ITEMS; ++k) { x[k] = i0 + k < n ? (S)fn(i0 + k) : 0; s += x[k]; }
+    S at = bsum[blockIdx.x] + block_inclusive_scan(s, lds) - s;
 #pragma unroll
     for (int k = 0; k < MT_ITEMS; ++k) {
-        if (i0 + k < n) pos[i0 + k] = at;
-        at += fl[k];
+        if (i0 + k < n) {
+            out[i0 + k] = at;
+            if constexpr (!std::is_same<Copy, std::nullptr_t>::value) copy[i0 + k] = at;
+        }
+        at += x[k];
     }
 }
 
-// pos[i] = the number of j < i with pred(j); *total = the number of all.  bsum: blocks_of(n, MT_CHUNK) int32.
-template <class P>
-void scan_launch(P pred, int64_t n, int32_t *bsum, int32_t *pos, int32_t *total, hipStream_t st) {
+// out[i] = the sum of fn(j) over j < i; *total = the sum over all.  copy: a second S * that gets out's words in the same launch, or
+// nullptr for none (the literal: its type decides, so a scan without a copy carries no test for one).
+// bsum: blocks_of(n, MT_CHUNK) words of S (scan_bytes<S>).
+template <class Fn, class S, class Copy = std::nullptr_t>
+void scan_launch(Fn fn, int64_t n, S *bsum, S *out, S *total, hipStream_t st, Copy copy = nullptr) {
     const unsigned nb = blocks_of(n, MT_CHUNK);
-    hipLaunchKernelGGL(scan_count_kernel<P>, dim3(nb), dim3(MT_THREADS), 0, st, pred, n, bsum);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(MT_THREADS), 0, st, bsum, (int)nb, total);
-    hipLaunchKernelGGL(scan_write_kernel<P>, dim3(nb), dim3(MT_THREADS), 0, st, pred, n, (const int32_t *)bsum, pos);
+    hipLaunchKernelGGL((scan_count_kernel<Fn, S>), dim3(nb), dim3(MT_THREADS), 0, st, fn, n, bsum);
+    hipLaunchKernelGGL(scan_blocks_kernel<S>, dim3(1), dim3(MT_THREADS), 0, st, bsum, (int)nb, total);
+    hipLaunchKernelGGL((scan_write_kernel<Fn, S, Copy>), dim3(nb), dim3(MT_THREADS), 0, st, fn, n, (const S *)bsum, out, copy);
 }
 
-size_t scan_bytes(int64_t n) { return up256((size_t)blocks_of(n, MT_CHUNK) * sizeof(int32_t)); }
+template <class S = int32_t>
+size_t scan_bytes(int64_t n) { return up256((size_t)blocks_of(n, MT_CHUNK) * sizeof(S)); }
 
 // ---- per-(wave, component) combination ------------------------------------------------------------------------------------------------------
 // Every lane holds K 64-bit values for component `cur` (cur < 0: nothing).  Lanes with one component are combined by Op and the first of
@@ -191,6 +205,27 @@ __device__ inline void limbs_of(double x, int e, u64 &hi, u64 &lo) {
 __device__ inline double sum_of(u64 hi, u64 lo, int e) {
     const double s = (double)(long long)hi + ldexp((double)(long long)lo, -31);
     return ldexp(s, e - 30);
+}
+
+// ---- host helpers ------------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(MT_THREADS) copy_words_kernel(const uint32_t *src, int64_t n, uint32_t *dst) {
+    const int64_t i = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
+    if (i < n) dst[i] = src[i];
+}
+
+// bytes / 4 dwords from src to dst, on the stream (a launch like its neighbours: no host-side copy engine in between)
+void copy_words(const void *src, size_t bytes, void *dst, hipStream_t st) {
+    const int64_t n = (int64_t)(bytes / 4);
+    if (n) hipLaunchKernelGGL(copy_words_kernel, dim3(blocks_of(n, MT_THREADS)), dim3(MT_THREADS), 0, st, static_cast<const uint32_t *>(src), n,
+                              static_cast<uint32_t *>(dst));
+}
+
+// the first N status words of a workspace to the host: one copy, one wait
+template <int N>
+int read_status(const void *workspace, int32_t (&h)[N], hipStream_t st, const char *where) {
+    hipError_t e = hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return vt_check(e, where);
 }
 
 }  // namespace

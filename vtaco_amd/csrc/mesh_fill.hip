@@ -1,9 +1,8 @@
 // Hole filling of a triangle mesh on the device: the boundary half-edges, their loops, and the cap of every loop (DESIGN.md, section
 // "mesh_fill.hip"; tests/mesh_fill_ref.py is the definition, and every output equals it bit for bit).  faces [F,3] i32 over V vertices,
 // f32 or f64.  Half-edge h = 3 f + k runs from faces[f][k] (tail) to faces[f][(k+1)%3] (head); flat, its tail is faces[h].
-//   edge table    mesh_topo.hip's construction once more: 64-bit keys (lo << 32 | hi) in 4 F slots rounded up to a power of two, claimed by
-//                 atomicCAS; the value counts lo -> hi uses in its low word, hi -> lo in its high word.  A half-edge is a boundary half-edge
-//                 when its edge's two counts add up to 1 (its own use).  One byte per half-edge, then scan_launch over the 3 F bytes: the
+//   edge table    mesh_edges.h's table.  A half-edge is a boundary half-edge when its edge's two counts add up to 1 (its own use).
+//                 One byte per half-edge, then scan_launch (mesh_common.h) over the 3 F bytes: the
 //                 compacted list keeps half-edge order, so "lowest compacted index" and "lowest half-edge" are one thing from here on.
 //   degrees       per vertex the boundary half-edges out of it and into it (integer atomicAdd) and the lowest one out of it (atomicMin).
 //                 succ[i] = that one at head(i) when the head has one of each, DEAD otherwise.  succ is injective where defined: only
@@ -15,7 +14,7 @@
 //                 A second run of R rounds over the cycles cut in front of their heads adds up distances: d = the steps to the loop's
 //                 last element, so the position of i is d[head] - d[i] and the loop's length d[head] + 1.  All 2 R rounds are enqueued
 //                 at once; no round is read back.
-//   outputs       one 64-bit scan over the list, (1 << 32 | length) at the heads: the loop number and the loop's offset of every head.
+//   outputs       one scan_launch with u64 sums over the list, (1 << 32 | length) at the heads: the loop number and the loop's offset of every head.
 //   emit          per loop (new vertices << 32 | new faces), scanned; one lane per new face finds its loop by bisection of the scanned
 //                 face offsets.  The centroid is mesh_topo.hip's exact sum: the largest |coordinate| of the loop by atomicMax on the bit
 //                 pattern, then every coordinate as two int64 fixed-point limbs by integer atomicAdd, rounded once, divided by n in
@@ -27,6 +26,7 @@
 #include <type_traits>
 
 #include "mesh_common.h"
+#include "mesh_edges.h"
 #include "vt_common.h"
 #include "vtaco_hip.h"
 
@@ -35,131 +35,19 @@ namespace {
 // int32 words of the status block; ST_TOTAL is the index of a 64-bit word (bytes 64..71)
 enum { ST_BAD = 0, ST_NB = 8, ST_NFILLED = 9, ST_TOTAL = 8 };
 constexpr int DEAD = -1;
-constexpr u64 EDGE_EMPTY = ~0ull;
-
-int64_t edge_slots(int64_t F) {
-    int64_t cap = 1024;
-    while (cap < 4 * F) cap <<= 1;
-    return cap;
-}
-
-// ---- a 64-bit exclusive scan of values: mesh_common.h's predicate scan with u64 sums (two 32-bit fields are scanned at once) -------------
-__device__ inline u64 block_inclusive_scan64(u64 x, u64 *lds) {
-    __syncthreads();
-    lds[threadIdx.x] = x;
-    __syncthreads();
-    for (int d = 1; d < MT_THREADS; d <<= 1) {
-        const u64 y = (int)threadIdx.x >= d ? lds[threadIdx.x - d] : 0;
-        __syncthreads();
-        lds[threadIdx.x] += y;
-        __syncthreads();
-    }
-    return lds[threadIdx.x];
-}
-
-template <class Fn>
-__global__ void __launch_bounds__(MT_THREADS) vscan_count_kernel(Fn fn, int64_t n, u64 *bsum) {
-    __shared__ u64 lds[MT_THREADS];
-    const int64_t i0 = (int64_t)blockIdx.x * MT_CHUNK + (int64_t)threadIdx.x * MT_ITEMS;
-    u64 s = 0;
-#pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) s += i0 + k < n ? fn(i0 + k) : 0;
-    const u64 incl = block_inclusive_scan64(s, lds);
-    if (threadIdx.x == MT_THREADS - 1) bsum[blockIdx.x] = incl;
-}
-
-__global__ void __launch_bounds__(MT_THREADS) vscan_blocks_kernel(u64 *bsum, int nb, u64 *total) {
-    __shared__ u64 lds[MT_THREADS];
-    u64 carry = 0;
-    for (int base = 0; base < nb; base += MT_THREADS) {
-        const int i = base + (int)threadIdx.x;
-        const u64 x = i < nb ? bsum[i] : 0;
-        const u64 incl = block_inclusive_scan64(x, lds);
-        if (i < nb) bsum[i] = carry + incl - x;
-        carry += lds[MT_THREADS - 1];
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-template <class Fn>
-__global__ void __launch_bounds__(MT_THREADS) vscan_write_kernel(Fn fn, int64_t n, const u64 *bsum, u64 *out) {
-    __shared__ u64 lds[MT_THREADS];
-    const int64_t i0 = (int64_t)blockIdx.x * MT_CHUNK + (int64_t)threadIdx.x * MT_ITEMS;
-    u64 x[MT_ITEMS];
-    u64 s = 0;
-#pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) { x[k] = i0 + k < n ? fn(i0 + k) : 0; s += x[k]; }
-    u64 at = bsum[blockIdx.x] + block_inclusive_scan64(s, lds) - s;
-#pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) {
-        if (i0 + k < n) out[i0 + k] = at;
-        at += x[k];
-    }
-}
-
-// out[i] = the sum of fn(j) over j < i; *total = the sum over all.  bsum: blocks_of(n, MT_CHUNK) u64.
-template <class Fn>
-void vscan_launch(Fn fn, int64_t n, u64 *bsum, u64 *out, u64 *total, hipStream_t st) {
-    const unsigned nb = blocks_of(n, MT_CHUNK);
-    hipLaunchKernelGGL(vscan_count_kernel<Fn>, dim3(nb), dim3(MT_THREADS), 0, st, fn, n, bsum);
-    hipLaunchKernelGGL(vscan_blocks_kernel, dim3(1), dim3(MT_THREADS), 0, st, bsum, (int)nb, total);
-    hipLaunchKernelGGL(vscan_write_kernel<Fn>, dim3(nb), dim3(MT_THREADS), 0, st, fn, n, (const u64 *)bsum, out);
-}
-
-size_t vscan_bytes(int64_t n) { return up256((size_t)blocks_of(n, MT_CHUNK) * sizeof(u64)); }
 
 // ---- stage 1: the edge table and the boundary flags ----------------------------------------------------------------------------------------
-__device__ inline u64 edge_key(int a, int b) { return a < b ? ((u64)(unsigned)a << 32 | (unsigned)b) : ((u64)(unsigned)b << 32 | (unsigned)a); }
-
-__device__ inline void edge_insert(u64 *keys, u64 *vals, u64 mask, int shift, int a, int b) {
-    if (a == b) return;
-    const u64 key = edge_key(a, b);
-    const u64 inc = a < b ? 1ull : (1ull << 32);
-    u64 slot = (key * 0x9E3779B97F4A7C15ull) >> shift;
-    for (u64 probes = 0; probes <= mask; ++probes) {          // (at most 3 F of the >= 4 F slots are ever claimed: a free one is met)
-        const u64 old = atomicCAS(keys + slot, EDGE_EMPTY, key);
-        if (old == EDGE_EMPTY || old == key) { atomicAdd(vals + slot, inc); return; }
-        slot = (slot + 1) & mask;
-    }
-}
-
-// the uses of {a, b}, both directions added; 0 for a == b and for a key that is not in the table
-__device__ inline u64 edge_uses(const u64 *keys, const u64 *vals, u64 mask, int shift, int a, int b) {
-    if (a == b) return 0;
-    const u64 key = edge_key(a, b);
-    u64 slot = (key * 0x9E3779B97F4A7C15ull) >> shift;
-    for (u64 probes = 0; probes <= mask; ++probes) {
-        const u64 k = keys[slot];
-        if (k == key) { const u64 v = vals[slot]; return (v & 0xffffffffull) + (v >> 32); }
-        if (k == EDGE_EMPTY) return 0;
-        slot = (slot + 1) & mask;
-    }
-    return 0;
-}
-
 __global__ void __launch_bounds__(MT_THREADS)
-edge_insert_kernel(const int32_t *faces, int F, int V, u64 *keys, u64 *vals, u64 mask, int shift, int32_t *status) {
-    __shared__ int32_t lds[MT_THREADS * 3];
-    int f, a, b, c;
-    bool ok;
-    if (!load_face(faces, F, V, lds, f, a, b, c, ok)) return;
-    if (!ok) { atomicOr(status + ST_BAD, 1); return; }
-    edge_insert(keys, vals, mask, shift, a, b);
-    edge_insert(keys, vals, mask, shift, b, c);
-    edge_insert(keys, vals, mask, shift, c, a);
-}
-
-__global__ void __launch_bounds__(MT_THREADS)
-edge_flag_kernel(const int32_t *faces, int F, int V, const u64 *keys, const u64 *vals, u64 mask, int shift, uint8_t *flag) {
+edge_flag_kernel(const int32_t *faces, int F, int V, EdgeTable t, uint8_t *flag) {
     __shared__ int32_t lds[MT_THREADS * 3];
     int f, a, b, c;
     bool ok;
     if (!load_face(faces, F, V, lds, f, a, b, c, ok)) return;
     uint8_t f0 = 0, f1 = 0, f2 = 0;
     if (ok) {
-        f0 = edge_uses(keys, vals, mask, shift, a, b) == 1;
-        f1 = edge_uses(keys, vals, mask, shift, b, c) == 1;
-        f2 = edge_uses(keys, vals, mask, shift, c, a) == 1;
+        f0 = edge_uses(t, a, b) == 1;
+        f1 = edge_uses(t, b, c) == 1;
+        f2 = edge_uses(t, c, a) == 1;
     }
     uint8_t *p = flag + (size_t)f * 3;                         // f < F: inside the 3 F bytes
     p[0] = f0; p[1] = f1; p[2] = f2;
@@ -384,22 +272,17 @@ centroid_finish_kernel(const int32_t *off, const u64 *fv, int L, int V, int NNV,
     }
 }
 
-__global__ void __launch_bounds__(MT_THREADS) copy_words_kernel(const uint32_t *src, int64_t n, uint32_t *dst) {
-    const int64_t i = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
-    if (i < n) dst[i] = src[i];
-}
-
 // ---- the workspaces -----------------------------------------------------------------------------------------------------------------------------
 bool sizes_ok(int64_t V, int64_t F) { return V >= 1 && F >= 1 && V <= MT_MAX_V && F <= MT_MAX_F; }
 
 // status | table, later the two doubling buffers B, C | pos, later the doubling buffer A | flag | bhe | succ | vout, vin, vfirst | scan sums
 struct BoundaryWs {
     int32_t *status;
-    u64 *keys, *vals, *vsum, *total;
+    EdgeTable t;
+    u64 *vsum, *total;
     int2 *bufA, *bufB, *bufC;
     int32_t *pos, *bhe, *succ, *vout, *vin, *vfirst, *bsum;
     uint8_t *flag;
-    int64_t slots;
     size_t bytes;
 };
 
@@ -408,13 +291,11 @@ BoundaryWs boundary_ws(void *workspace, int64_t V, int64_t F) {
     const int64_t H = 3 * F;
     char *p = static_cast<char *>(workspace);
     size_t at = 0;
-    w.slots = edge_slots(F);
     w.status = reinterpret_cast<int32_t *>(p);
     w.total = reinterpret_cast<u64 *>(p + ST_TOTAL * 8);
     at += MT_STATUS_BYTES;
-    const size_t table = (size_t)w.slots * 16, two = 2 * up256((size_t)H * 8);
-    w.keys = reinterpret_cast<u64 *>(p + at);
-    w.vals = w.keys + w.slots;
+    w.t = edge_table_at(p + at, F);
+    const size_t table = (size_t)w.t.slots * 16, two = 2 * up256((size_t)H * 8);
     w.bufB = reinterpret_cast<int2 *>(p + at);
     w.bufC = reinterpret_cast<int2 *>(p + at + up256((size_t)H * 8));
     at += table > two ? table : two;
@@ -428,7 +309,7 @@ BoundaryWs boundary_ws(void *workspace, int64_t V, int64_t F) {
     w.vin = reinterpret_cast<int32_t *>(p + at); at += up256((size_t)V * 4);
     w.vfirst = reinterpret_cast<int32_t *>(p + at); at += up256((size_t)V * 4);
     w.bsum = reinterpret_cast<int32_t *>(p + at); at += scan_bytes(H);
-    w.vsum = reinterpret_cast<u64 *>(p + at); at += vscan_bytes(H);
+    w.vsum = reinterpret_cast<u64 *>(p + at); at += scan_bytes<u64>(H);
     w.bytes = at;
     return w;
 }
@@ -446,17 +327,11 @@ FillWs fill_ws(void *workspace, int64_t L) {
     w.status = reinterpret_cast<int32_t *>(p);
     at += MT_STATUS_BYTES;
     w.fv = reinterpret_cast<u64 *>(p + at); at += up256((size_t)(L + 1) * 8);
-    w.vsum = reinterpret_cast<u64 *>(p + at); at += vscan_bytes(L);
+    w.vsum = reinterpret_cast<u64 *>(p + at); at += scan_bytes<u64>(L);
     w.cmax = reinterpret_cast<u64 *>(p + at); at += up256((size_t)L * 3 * 8);
     w.csum = reinterpret_cast<u64 *>(p + at); at += up256((size_t)L * 6 * 8);
     w.bytes = at;
     return w;
-}
-
-int read_status(const void *workspace, int32_t (&h)[32], hipStream_t st, const char *where) {
-    hipError_t e = hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return vt_check(e, where);
 }
 
 int64_t total_of(const int32_t (&h)[32], int word) { return (int64_t)(uint32_t)h[ST_TOTAL * 2 + word]; }     // word 0: low half
@@ -468,12 +343,6 @@ void centroid_launch(const T *verts, int V, const int32_t *off, const int32_t *l
     hipLaunchKernelGGL((centroid_kernel<T, 1>), grid, block, 0, st, verts, V, off, lv, (const u64 *)w.fv, L, NNF, NNV, w.cmax, w.csum);
     hipLaunchKernelGGL(centroid_finish_kernel<T>, dim3(blocks_of(L, MT_THREADS)), block, 0, st, off, (const u64 *)w.fv, L, V, NNV, (const u64 *)w.cmax,
                        (const u64 *)w.csum, out_verts);
-}
-
-void copy_words(const void *src, size_t bytes, void *dst, hipStream_t st) {
-    const int64_t n = (int64_t)(bytes / 4);
-    if (n) hipLaunchKernelGGL(copy_words_kernel, dim3(blocks_of(n, MT_THREADS)), dim3(MT_THREADS), 0, st, static_cast<const uint32_t *>(src), n,
-                              static_cast<uint32_t *>(dst));
 }
 
 }  // namespace
@@ -488,16 +357,12 @@ int vt_mesh_boundary(const int32_t *faces, int64_t F, int64_t V, int *n_boundary
     hipStream_t st = (hipStream_t)stream;
     const BoundaryWs w = boundary_ws(workspace, V, F);
     const int64_t H = 3 * F;
-    int shift = 64;
-    for (int64_t s = w.slots; s > 1; s >>= 1) --shift;            // slots = 2^(64 - shift)
     int rc = vt_fill32(w.status, 0u, MT_STATUS_BYTES, st);
-    if (!rc) rc = vt_fill32(w.keys, 0xffffffffu, (size_t)w.slots * 8, st);
-    if (!rc) rc = vt_fill32(w.vals, 0u, (size_t)w.slots * 8, st);
+    if (!rc) rc = edge_table_clear(w.t, st);
     if (rc) return rc;
     const dim3 block(MT_THREADS), fgrid(blocks_of(F, MT_THREADS));
-    hipLaunchKernelGGL(edge_insert_kernel, fgrid, block, 0, st, faces, (int)F, (int)V, w.keys, w.vals, (u64)(w.slots - 1), shift, w.status);
-    hipLaunchKernelGGL(edge_flag_kernel, fgrid, block, 0, st, faces, (int)F, (int)V, (const u64 *)w.keys, (const u64 *)w.vals, (u64)(w.slots - 1), shift,
-                       w.flag);
+    hipLaunchKernelGGL(edge_insert_kernel<true>, fgrid, block, 0, st, faces, (int)F, (int)V, w.t, w.status + ST_BAD);
+    hipLaunchKernelGGL(edge_flag_kernel, fgrid, block, 0, st, faces, (int)F, (int)V, w.t, w.flag);
     scan_launch(FlagPred{w.flag}, H, w.bsum, w.pos, w.status + ST_NB, st);
     hipLaunchKernelGGL(compact_kernel, dim3(blocks_of(H, MT_THREADS)), block, 0, st, (const uint8_t *)w.flag, (const int32_t *)w.pos, H, w.bhe);
     rc = vt_check(hipGetLastError(), "vt_mesh_boundary");
@@ -546,7 +411,7 @@ int vt_mesh_boundary_loops(const int32_t *faces, int64_t F, int64_t V, int64_t N
     }
     const int2 *ranks = cur;
     u64 *scan = reinterpret_cast<u64 *>(other);
-    vscan_launch(HeadFn{mins, ranks}, NB, w.vsum, scan, w.total, st);
+    scan_launch(HeadFn{mins, ranks}, NB, w.vsum, scan, w.total, st);
     hipLaunchKernelGGL(loops_write_kernel, grid, block, 0, st, faces, (const int32_t *)w.bhe, mins, ranks, (const u64 *)scan, (const u64 *)w.total, n,
                        loop_offsets, loop_vertices, loop_half_edges);
     int rc = vt_check(hipGetLastError(), "vt_mesh_boundary_loops");
@@ -573,7 +438,7 @@ int vt_mesh_fill_count(const int32_t *loop_offsets, int64_t L, int method, int64
     int rc = vt_fill32(w.status, 0u, MT_STATUS_BYTES, st);
     if (rc) return rc;
     const FillFn fn{loop_offsets, method, max_edges};
-    vscan_launch(fn, L, w.vsum, w.fv, w.fv + L, st);
+    scan_launch(fn, L, w.vsum, w.fv, w.fv + L, st);
     hipLaunchKernelGGL(filled_count_kernel, dim3(blocks_of(L, MT_THREADS)), dim3(MT_THREADS), 0, st, fn, (int)L, w.status);
     rc = vt_check(hipGetLastError(), "vt_mesh_fill_count");
     if (rc) return rc;

@@ -586,8 +586,8 @@ int vt_mesh_cluster_faces(const int32_t *faces, int64_t F, int64_t V, const int3
                            (const int32_t *)fpos, out_faces);
     } else {                                      // the count alone: the scan's first two launches
         const unsigned nb = blocks_of(F, MT_CHUNK);
-        hipLaunchKernelGGL(scan_count_kernel<FaceKeptPred>, dim3(nb), dim3(MT_THREADS), 0, st, kept, F, bsum);
-        hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(MT_THREADS), 0, st, bsum, (int)nb, state + SS_NF);
+        hipLaunchKernelGGL((scan_count_kernel<FaceKeptPred, int32_t>), dim3(nb), dim3(MT_THREADS), 0, st, kept, F, bsum);
+        hipLaunchKernelGGL(scan_blocks_kernel<int32_t>, dim3(1), dim3(MT_THREADS), 0, st, bsum, (int)nb, state + SS_NF);
     }
     rc = vt_check(hipGetLastError(), "vt_mesh_cluster_faces");
     if (rc) return rc;

@@ -1,12 +1,11 @@
 // Vertex adjacency of a triangle mesh as CSR rows, and the Laplacian-type smoothing filters that walk them (DESIGN.md, section
 // "mesh_smooth.hip"; tests/mesh_smooth_ref.py is the definition, and every output equals it bit for bit).  faces [F,3] i32 over V vertices.
-//   edge table    mesh_topo.hip's construction once more (a private copy, as mesh_fill.hip keeps one): 64-bit keys (lo << 32 | hi) in 4 F
-//                 slots rounded up to a power of two, claimed by atomicCAS; the value counts the uses of the edge.  Every claimed slot is
-//                 one undirected edge {a, b}, a != b, however many faces share it.
-//   count         one lane per slot: integer atomicAdd on the degrees of a and b; a value scan of the degrees gives offsets [V+1], and its
-//                 total, nnz = 2 E <= 6 F, is the one word the host reads.
+//   edge table    mesh_edges.h's table.  Every claimed slot is one undirected edge {a, b}, a != b, however many faces share it.
+//   count         one lane per slot: integer atomicAdd on the degrees of a and b; scan_launch (mesh_common.h) over the degrees gives
+//                 offsets [V+1], in the caller's array and in the workspace at once, and its total, nnz = 2 E <= 6 F, is the one word
+//                 the host reads.
 //   fill          one lane per slot again: each end takes the next free place of its row from a per-vertex cursor (integer atomicAdd) and
-//                 stores the other end and the edge's boundary bit (uses == 1) in a scratch row.  The order within a row is whatever the
+//                 stores the other end and the edge's boundary bit (edge_uses == 1) in a scratch row.  The order within a row is whatever the
 //                 atomics gave, so one lane per entry then counts the row's entries below its own -- they are distinct: the count is the
 //                 entry's place in ascending order -- and writes neighbors / boundary_edge there.  boundary_vertex is the OR of the row's bits.
 //   filter        positions live in float64 buffers of the workspace for all passes and are rounded once at the end.  One lane per vertex
@@ -19,6 +18,7 @@
 #include <stdint.h>
 
 #include "mesh_common.h"
+#include "mesh_edges.h"
 #include "vt_common.h"
 #include "vtaco_hip.h"
 
@@ -27,38 +27,7 @@ namespace {
 enum { ST_BAD = 0, ST_NNZ = 1 };                                  // int32 words of the status block
 enum { LAPLACIAN = 0, TAUBIN = 1, HUMPHREY = 2 };
 enum { PIN = 0, FREE = 1, LOOP = 2 };
-constexpr u64 EDGE_EMPTY = ~0ull;
 constexpr int64_t SM_MAX_F = 0x7fffffff / 6;                       // nnz <= 6 F stays an int32
-
-int64_t edge_slots(int64_t F) {
-    int64_t cap = 1024;
-    while (cap < 4 * F) cap <<= 1;
-    return cap;
-}
-
-// ---- the edge table ------------------------------------------------------------------------------------------------------------------------
-__device__ inline void edge_insert(u64 *keys, u64 *vals, u64 mask, int shift, int a, int b) {
-    if (a == b) return;
-    const u64 key = a < b ? ((u64)(unsigned)a << 32 | (unsigned)b) : ((u64)(unsigned)b << 32 | (unsigned)a);
-    u64 slot = (key * 0x9E3779B97F4A7C15ull) >> shift;
-    for (u64 probes = 0; probes <= mask; ++probes) {              // (at most 3 F of the >= 4 F slots are ever claimed: a free one is met)
-        const u64 old = atomicCAS(keys + slot, EDGE_EMPTY, key);
-        if (old == EDGE_EMPTY || old == key) { atomicAdd(vals + slot, 1ull); return; }
-        slot = (slot + 1) & mask;
-    }
-}
-
-__global__ void __launch_bounds__(MT_THREADS)
-edge_insert_kernel(const int32_t *faces, int F, int V, u64 *keys, u64 *vals, u64 mask, int shift, int32_t *status) {
-    __shared__ int32_t lds[MT_THREADS * 3];
-    int f, a, b, c;
-    bool ok;
-    if (!load_face(faces, F, V, lds, f, a, b, c, ok)) return;
-    if (!ok) { atomicOr(status + ST_BAD, 1); return; }
-    edge_insert(keys, vals, mask, shift, a, b);
-    edge_insert(keys, vals, mask, shift, b, c);
-    edge_insert(keys, vals, mask, shift, c, a);
-}
 
 // (keys hold indices that passed load_face's test: both ends lie in [0, V))
 __global__ void __launch_bounds__(MT_THREADS) degree_kernel(const u64 *keys, int64_t slots, int32_t *deg) {
@@ -70,37 +39,12 @@ __global__ void __launch_bounds__(MT_THREADS) degree_kernel(const u64 *keys, int
     atomicAdd(deg + (int)(unsigned)key, 1);
 }
 
-// ---- an exclusive scan of int32 values: mesh_common.h's predicate scan with values --------------------------------------------------------
+// ---- count ------------------------------------------------------------------------------------------------------------------------------------
 struct DegreeFn {                                                  // element V is 0: the scan's word V is the total
     const int32_t *deg;
     int64_t V;
     __device__ int operator()(int64_t i) const { return i < V ? deg[i] : 0; }
 };
-
-__global__ void __launch_bounds__(MT_THREADS) iscan_count_kernel(DegreeFn fn, int64_t n, int32_t *bsum) {
-    __shared__ int lds[MT_THREADS];
-    const int64_t i0 = (int64_t)blockIdx.x * MT_CHUNK + (int64_t)threadIdx.x * MT_ITEMS;
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) s += i0 + k < n ? fn(i0 + k) : 0;
-    const int incl = block_inclusive_scan(s, lds);
-    if (threadIdx.x == MT_THREADS - 1) bsum[blockIdx.x] = incl;
-}
-
-__global__ void __launch_bounds__(MT_THREADS) iscan_write_kernel(DegreeFn fn, int64_t n, const int32_t *bsum, int32_t *out, int32_t *copy) {
-    __shared__ int lds[MT_THREADS];
-    const int64_t i0 = (int64_t)blockIdx.x * MT_CHUNK + (int64_t)threadIdx.x * MT_ITEMS;
-    int x[MT_ITEMS];
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) { x[k] = i0 + k < n ? fn(i0 + k) : 0; s += x[k]; }
-    int at = bsum[blockIdx.x] + block_inclusive_scan(s, lds) - s;
-#pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) {
-        if (i0 + k < n) { out[i0 + k] = at; copy[i0 + k] = at; }
-        at += x[k];
-    }
-}
 
 // ---- fill --------------------------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(MT_THREADS)
@@ -110,7 +54,7 @@ scatter_kernel(const u64 *keys, const u64 *vals, int64_t slots, int32_t *cursor,
     const u64 key = keys[s];
     if (key == EDGE_EMPTY) return;
     const int a = (int)(key >> 32), b = (int)(unsigned)key;
-    const uint8_t be = vals[s] == 1;
+    const uint8_t be = edge_uses(vals[s]) == 1;
     const int pa = atomicAdd(cursor + a, 1), pb = atomicAdd(cursor + b, 1);
     if ((unsigned)pa < (unsigned)nnz) { raw_nb[pa] = b; raw_be[pa] = be; }     // (a cursor ends at its row's end: the test never fails on
     if ((unsigned)pb < (unsigned)nnz) { raw_nb[pb] = a; raw_be[pb] = be; }     //  the workspace vt_mesh_adjacency_count left for these faces)
@@ -313,20 +257,14 @@ __global__ void __launch_bounds__(SM_LDS_THREADS) smooth_lds_kernel(Rows r, cons
     for (int i = threadIdx.x; i < n; i += SM_LDS_THREADS) out_verts[i] = (T)cur[i];
 }
 
-__global__ void __launch_bounds__(MT_THREADS) copy_words_kernel(const uint32_t *src, int64_t n, uint32_t *dst) {
-    const int64_t i = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
-    if (i < n) dst[i] = src[i];
-}
-
 // ---- the workspaces -----------------------------------------------------------------------------------------------------------------------------
 bool sizes_ok(int64_t V, int64_t F) { return V >= 1 && F >= 1 && V <= MT_MAX_V && F <= SM_MAX_F; }
 
 // status | table | degrees, later the cursors | offsets | the unsorted rows | scan sums
 struct AdjWs {
     int32_t *status, *deg, *off, *raw_nb, *bsum;
-    u64 *keys, *vals;
+    EdgeTable t;
     uint8_t *raw_be;
-    int64_t slots;
     size_t bytes;
 };
 
@@ -334,10 +272,8 @@ AdjWs adj_ws(void *workspace, int64_t V, int64_t F) {
     AdjWs w;
     char *p = static_cast<char *>(workspace);
     size_t at = 0;
-    w.slots = edge_slots(F);
     w.status = reinterpret_cast<int32_t *>(p); at += MT_STATUS_BYTES;
-    w.keys = reinterpret_cast<u64 *>(p + at);
-    w.vals = w.keys + w.slots; at += (size_t)w.slots * 16;
+    w.t = edge_table_at(p + at, F); at += (size_t)w.t.slots * 16;
     w.deg = reinterpret_cast<int32_t *>(p + at); at += up256((size_t)(V + 1) * 4);
     w.off = reinterpret_cast<int32_t *>(p + at); at += up256((size_t)(V + 1) * 4);
     w.raw_nb = reinterpret_cast<int32_t *>(p + at); at += up256((size_t)F * 6 * 4);
@@ -401,28 +337,18 @@ int vt_mesh_adjacency_count(const int32_t *faces, int64_t F, int64_t V, int32_t 
     if (!workspace || workspace_bytes < adj_ws(nullptr, V, F).bytes) return vt_fail(VT_ERR_WORKSPACE, "vt_mesh_adjacency_count");
     hipStream_t st = (hipStream_t)stream;
     const AdjWs w = adj_ws(workspace, V, F);
-    int shift = 64;
-    for (int64_t s = w.slots; s > 1; s >>= 1) --shift;            // slots = 2^(64 - shift)
     int rc = vt_fill32(w.status, 0u, MT_STATUS_BYTES, st);
-    if (!rc) rc = vt_fill32(w.keys, 0xffffffffu, (size_t)w.slots * 8, st);
-    if (!rc) rc = vt_fill32(w.vals, 0u, (size_t)w.slots * 8, st);
+    if (!rc) rc = edge_table_clear(w.t, st);
     if (!rc) rc = vt_fill32(w.deg, 0u, up256((size_t)(V + 1) * 4), st);
     if (rc) return rc;
     const dim3 block(MT_THREADS);
-    hipLaunchKernelGGL(edge_insert_kernel, dim3(blocks_of(F, MT_THREADS)), block, 0, st, faces, (int)F, (int)V, w.keys, w.vals, (u64)(w.slots - 1), shift,
-                       w.status);
-    hipLaunchKernelGGL(degree_kernel, dim3(blocks_of(w.slots, MT_THREADS)), block, 0, st, (const u64 *)w.keys, w.slots, w.deg);
-    const DegreeFn fn{w.deg, V};
-    const unsigned nb = blocks_of(V + 1, MT_CHUNK);
-    hipLaunchKernelGGL(iscan_count_kernel, dim3(nb), block, 0, st, fn, V + 1, w.bsum);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), block, 0, st, w.bsum, (int)nb, w.status + ST_NNZ);
-    hipLaunchKernelGGL(iscan_write_kernel, dim3(nb), block, 0, st, fn, V + 1, (const int32_t *)w.bsum, offsets, w.off);
+    hipLaunchKernelGGL(edge_insert_kernel<true>, dim3(blocks_of(F, MT_THREADS)), block, 0, st, faces, (int)F, (int)V, w.t, w.status + ST_BAD);
+    hipLaunchKernelGGL(degree_kernel, dim3(blocks_of(w.t.slots, MT_THREADS)), block, 0, st, (const u64 *)w.t.keys, w.t.slots, w.deg);
+    scan_launch(DegreeFn{w.deg, V}, V + 1, w.bsum, offsets, w.status + ST_NNZ, st, w.off);
     rc = vt_check(hipGetLastError(), "vt_mesh_adjacency_count");
     if (rc) return rc;
     int32_t h[32];
-    hipError_t e = hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    rc = vt_check(e, "vt_mesh_adjacency_count");
+    rc = read_status(workspace, h, st, "vt_mesh_adjacency_count");
     if (rc) return rc;
     if (h[ST_BAD]) return vt_fail(VT_ERR_INVALID, "vt_mesh_adjacency_count: a face index lies outside [0, V)");
     if (h[ST_NNZ] < 0 || h[ST_NNZ] > 6 * F) return vt_fail(VT_ERR_INVALID, "vt_mesh_adjacency_count: nnz outside [0, 6 F]");
@@ -439,9 +365,8 @@ int vt_mesh_adjacency_fill(int64_t F, int64_t V, int64_t nnz, int32_t *neighbors
     const AdjWs w = adj_ws(workspace, V, F);
     const dim3 block(MT_THREADS);
     // the cursors start at the rows' offsets (the degrees are not needed again)
-    hipLaunchKernelGGL(copy_words_kernel, dim3(blocks_of(V, MT_THREADS)), block, 0, st, reinterpret_cast<const uint32_t *>(w.off), V,
-                       reinterpret_cast<uint32_t *>(w.deg));
-    hipLaunchKernelGGL(scatter_kernel, dim3(blocks_of(w.slots, MT_THREADS)), block, 0, st, (const u64 *)w.keys, (const u64 *)w.vals, w.slots, w.deg,
+    copy_words(w.off, (size_t)V * 4, w.deg, st);
+    hipLaunchKernelGGL(scatter_kernel, dim3(blocks_of(w.t.slots, MT_THREADS)), block, 0, st, (const u64 *)w.t.keys, (const u64 *)w.t.vals, w.t.slots, w.deg,
                        (int)nnz, w.raw_nb, w.raw_be);
     hipLaunchKernelGGL(rank_kernel, dim3(blocks_of(nnz, MT_THREADS)), block, 0, st, (const int32_t *)w.off, (int)V, (int)nnz, (const int32_t *)w.raw_nb,
                        (const uint8_t *)w.raw_be, neighbors, boundary_edge);
@@ -475,9 +400,7 @@ int vt_mesh_smooth(const void *verts, int verts_f64, int64_t V, const int32_t *o
     if (!(lam == lam) || !(mu == mu) || !(alpha == alpha) || !(beta == beta)) return vt_fail(VT_ERR_INVALID, "vt_mesh_smooth: a NaN coefficient");
     hipStream_t st = (hipStream_t)stream;
     if (iterations == 0 || nnz == 0) {                             // nothing moves: the input's bits
-        const int64_t n = V * 3 * (verts_f64 ? 2 : 1);
-        hipLaunchKernelGGL(copy_words_kernel, dim3(blocks_of(n, MT_THREADS)), dim3(MT_THREADS), 0, st, static_cast<const uint32_t *>(verts), n,
-                           static_cast<uint32_t *>(out_verts));
+        copy_words(verts, (size_t)V * 3 * (verts_f64 ? 8 : 4), out_verts, st);
         return vt_check(hipGetLastError(), "vt_mesh_smooth");
     }
     const bool one = form == 2 || (form == 0 && V <= SM_LDS_MAX_V);

@@ -1,14 +1,13 @@
 // Subdivision of a triangle mesh on the device: mark a set of edges, give each marked edge one new vertex, split each face by how many of
 // its edges are marked (DESIGN.md, section "mesh_subdivide.hip"; tests/mesh_subdivide_ref.py is the definition, and every output equals
 // it bit for bit).  faces [F,3] i32 over V vertices, f32 or f64.  Half-edge h = 3 f + k runs from faces[f][k] to faces[f][(k+1)%3].
-//   edge table    mesh_fill.hip's construction once more: 64-bit keys (lo << 32 | hi) in 4 F slots rounded up to a power of two, claimed by
-//                 atomicCAS; the value counts lo -> hi uses in its low word, hi -> lo in its high word.  Per slot also the lowest and the
-//                 highest half-edge on the edge (integer atomicMin / atomicMax), and per half-edge its slot.
+//   edge table    mesh_edges.h's table.  Per slot also the lowest and the highest half-edge on the edge (integer atomicMin / atomicMax),
+//                 and per half-edge its slot.
 //   marks         mark 0 every edge; mark 1 an edge with (dx dx + dy dy) + dz dz > max_edge^2, d = x_hi - x_lo in double, evaluated once
 //                 by the edge's lowest half-edge from the lower index to the higher; mark 2 the edges of the faces with face_mask != 0
 //                 (atomicOr).  A half-edge is a first use when it is its edge's lowest half-edge and the edge is marked.
 //   numbering     scan_launch over the 3 F first-use bytes: marked edges are numbered in first-seen order, as a dict filled face by face
-//                 numbers them.  A value scan of 1 + marks(f) gives every face's output offset.  One host read returns the totals.
+//                 numbers them.  scan_launch again, over 1 + marks(f), gives every face's output offset.  One host read returns the totals.
 //   emit          one lane per face writes its 1 + marks children and their face_parent; one lane per first use writes the edge's
 //                 vertex and edge_verts; one lane per original vertex copies it (midpoint) or applies Loop's even rule over its CSR row.
 //   backward      g_v[i] = g[i] + 0.5 sum of g[V + e] over the edges at i, as mesh_normals.hip sums: the largest |term| per (vertex,
@@ -19,6 +18,7 @@
 #include <stdint.h>
 
 #include "mesh_common.h"
+#include "mesh_edges.h"
 #include "vt_common.h"
 #include "vtaco_hip.h"
 
@@ -27,34 +27,11 @@ namespace {
 enum { ST_BAD = 0, ST_NMARKED = 1, ST_NOUT = 2, ST_NIRR = 3 };     // int32 words of the status block
 enum { MARK_ALL = 0, MARK_LENGTH = 1, MARK_FACES = 2 };
 enum { MIDPOINT = 0, LOOP = 1 };
-constexpr u64 EDGE_EMPTY = ~0ull;
-constexpr uint32_t NO_SLOT = 0xffffffffu;                           // (slots <= 2^31)
-
-int64_t edge_slots(int64_t F) {
-    int64_t cap = 1024;
-    while (cap < 4 * F) cap <<= 1;
-    return cap;
-}
-
 // ---- the edge table ------------------------------------------------------------------------------------------------------------------------
-__device__ inline uint32_t edge_insert(u64 *keys, u64 *vals, u64 mask, int shift, int a, int b) {
-    const u64 key = a < b ? ((u64)(unsigned)a << 32 | (unsigned)b) : ((u64)(unsigned)b << 32 | (unsigned)a);
-    const u64 inc = a < b ? 1ull : (1ull << 32);
-    u64 slot = (key * 0x9E3779B97F4A7C15ull) >> shift;
-    for (u64 probes = 0; probes <= mask; ++probes) {              // (at most 3 F of the >= 4 F slots are ever claimed: a free one is met)
-        const u64 old = atomicCAS(keys + slot, EDGE_EMPTY, key);
-        if (old == EDGE_EMPTY || old == key) { atomicAdd(vals + slot, inc); return (uint32_t)slot; }
-        slot = (slot + 1) & mask;
-    }
-    return NO_SLOT;
-}
-
-struct Table {
-    u64 *keys, *vals;
+struct Table {                                                     // the shared table, four more words per slot, and per half-edge its slot
+    EdgeTable e;
     int32_t *minh, *maxh, *eid, *emark;
     uint32_t *he_slot;
-    u64 mask;
-    int shift;
 };
 
 __global__ void __launch_bounds__(MT_THREADS)
@@ -73,7 +50,7 @@ insert_kernel(const int32_t *faces, int F, int V, int mark, const uint8_t *face_
     const int tail[3] = {a, b, c}, head[3] = {b, c, a};
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const uint32_t slot = edge_insert(t.keys, t.vals, t.mask, t.shift, tail[k], head[k]);
+        const uint32_t slot = edge_insert(t.e, tail[k], head[k]);
         t.he_slot[h0 + k] = slot;
         if (slot == NO_SLOT) continue;
         atomicMin(t.minh + slot, (int)(h0 + k));
@@ -93,7 +70,7 @@ __global__ void __launch_bounds__(MT_THREADS) first_kernel(const T *verts, int64
         if (mark == MARK_ALL) out = 1;
         else if (mark == MARK_FACES) out = t.emark[slot] != 0;
         else {
-            const u64 key = t.keys[slot];                          // (both ends passed load_face's test)
+            const u64 key = t.e.keys[slot];                          // (both ends passed load_face's test)
             double x0, y0, z0, x1, y1, z1;
             load_vertex(verts, (int)(key >> 32), x0, y0, z0);
             load_vertex(verts, (int)(unsigned)key, x1, y1, z1);
@@ -115,12 +92,11 @@ __global__ void __launch_bounds__(MT_THREADS) number_kernel(int64_t n, const uin
     if (h >= n || !first[h]) return;
     const uint32_t slot = t.he_slot[h];
     t.eid[slot] = pos[h];
-    const u64 v = t.vals[slot];
+    const u64 v = t.e.vals[slot];
     const u64 fwd = v & 0xffffffffull, bwd = v >> 32;
     if (!(fwd <= 1 && bwd <= 1)) atomicAdd(status + ST_NIRR, 1);
 }
 
-// ---- an exclusive scan of int32 values (mesh_common.h's predicate scan with values) ------------------------------------------------------
 struct ChildrenFn {                                                // 1 + the marked edges of face f
     const uint32_t *he_slot;
     const int32_t *eid;
@@ -134,31 +110,6 @@ struct ChildrenFn {                                                // 1 + the ma
         return n;
     }
 };
-
-__global__ void __launch_bounds__(MT_THREADS) iscan_count_kernel(ChildrenFn fn, int64_t n, int32_t *bsum) {
-    __shared__ int lds[MT_THREADS];
-    const int64_t i0 = (int64_t)blockIdx.x * MT_CHUNK + (int64_t)threadIdx.x * MT_ITEMS;
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) s += i0 + k < n ? fn(i0 + k) : 0;
-    const int incl = block_inclusive_scan(s, lds);
-    if (threadIdx.x == MT_THREADS - 1) bsum[blockIdx.x] = incl;
-}
-
-__global__ void __launch_bounds__(MT_THREADS) iscan_write_kernel(ChildrenFn fn, int64_t n, const int32_t *bsum, int32_t *out) {
-    __shared__ int lds[MT_THREADS];
-    const int64_t i0 = (int64_t)blockIdx.x * MT_CHUNK + (int64_t)threadIdx.x * MT_ITEMS;
-    int x[MT_ITEMS];
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) { x[k] = i0 + k < n ? fn(i0 + k) : 0; s += x[k]; }
-    int at = bsum[blockIdx.x] + block_inclusive_scan(s, lds) - s;
-#pragma unroll
-    for (int k = 0; k < MT_ITEMS; ++k) {
-        if (i0 + k < n) out[i0 + k] = at;
-        at += x[k];
-    }
-}
 
 // ---- emit ------------------------------------------------------------------------------------------------------------------------------------
 __device__ inline void put_face(int32_t *out_faces, int32_t *face_parent, int64_t at, int f, int x, int y, int z) {
@@ -229,7 +180,7 @@ __global__ void __launch_bounds__(MT_THREADS) irregular_ends_kernel(int64_t n, c
     const int64_t h = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
     if (h >= n || !first[h]) return;
     const uint32_t slot = t.he_slot[h];
-    const u64 v = t.vals[slot], key = t.keys[slot];
+    const u64 v = t.e.vals[slot], key = t.e.keys[slot];
     if ((v & 0xffffffffull) <= 1 && (v >> 32) <= 1) return;
     const int lo = (int)(key >> 32), hi = (int)(unsigned)key;
     if ((unsigned)lo < (unsigned)V) atomicOr(virr + lo, 1);
@@ -246,7 +197,7 @@ edges_kernel(const T *verts, const int32_t *faces, int64_t n, int V, int scheme,
     const int e = pos[h];
     const uint32_t slot = t.he_slot[h];
     if ((unsigned)e >= (unsigned)n_marked || slot == NO_SLOT) return;
-    const u64 key = t.keys[slot];
+    const u64 key = t.e.keys[slot];
     const int lo = (int)(key >> 32), hi = (int)(unsigned)key;
     if ((unsigned)lo >= (unsigned)V || (unsigned)hi >= (unsigned)V) return;
     edge_verts[(size_t)e * 2] = lo;
@@ -261,7 +212,7 @@ edges_kernel(const T *verts, const int32_t *faces, int64_t n, int V, int scheme,
     double x0[3], x1[3];
     load_vertex(verts, lo, x0[0], x0[1], x0[2]);
     load_vertex(verts, hi, x1[0], x1[1], x1[2]);
-    const u64 v = t.vals[slot];
+    const u64 v = t.e.vals[slot];
     const int h1 = t.maxh[slot];
     if ((v & 0xffffffffull) == 1 && (v >> 32) == 1 && (unsigned)h1 < (unsigned)n && h1 != (int)h) {
         // exactly two half-edges lie on the edge: this one and the highest.  c is opposite in the lo -> hi face, d in the hi -> lo face.
@@ -326,11 +277,6 @@ even_kernel(const T *verts, int V, const int32_t *off, const int32_t *neighbors,
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) out[a] = keep ? src[a] : (T)r[a];
-}
-
-__global__ void __launch_bounds__(MT_THREADS) copy_words_kernel(const uint32_t *src, int64_t n, uint32_t *dst) {
-    const int64_t i = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
-    if (i < n) dst[i] = src[i];
 }
 
 // ---- the midpoint scheme over a batch, and its gradient -----------------------------------------------------------------------------------
@@ -414,8 +360,7 @@ struct SubWs {
     int32_t *status, *pos, *foff, *virr, *bsum;
     uint8_t *first;
     Table t;
-    int64_t slots;
-    size_t table_bytes, bytes;
+    size_t bytes;
 };
 
 SubWs sub_ws(void *workspace, int64_t V, int64_t F) {
@@ -423,24 +368,19 @@ SubWs sub_ws(void *workspace, int64_t V, int64_t F) {
     char *p = static_cast<char *>(workspace);
     size_t at = 0;
     const int64_t F1 = F < 1 ? 1 : F;
-    w.slots = edge_slots(F1);
     w.status = reinterpret_cast<int32_t *>(p); at += MT_STATUS_BYTES;
-    w.t.keys = reinterpret_cast<u64 *>(p + at); at += (size_t)w.slots * 8;
-    w.t.vals = reinterpret_cast<u64 *>(p + at); at += (size_t)w.slots * 8;
-    w.t.minh = reinterpret_cast<int32_t *>(p + at); at += (size_t)w.slots * 4;
-    w.t.maxh = reinterpret_cast<int32_t *>(p + at); at += (size_t)w.slots * 4;
-    w.t.eid = reinterpret_cast<int32_t *>(p + at); at += (size_t)w.slots * 4;
-    w.t.emark = reinterpret_cast<int32_t *>(p + at); at += (size_t)w.slots * 4;
-    w.table_bytes = at;
+    w.t.e = edge_table_at(p + at, F1); at += (size_t)w.t.e.slots * 16;
+    const size_t per_slot = (size_t)w.t.e.slots * 4;
+    w.t.minh = reinterpret_cast<int32_t *>(p + at); at += per_slot;
+    w.t.maxh = reinterpret_cast<int32_t *>(p + at); at += per_slot;
+    w.t.eid = reinterpret_cast<int32_t *>(p + at); at += per_slot;
+    w.t.emark = reinterpret_cast<int32_t *>(p + at); at += per_slot;
     w.t.he_slot = reinterpret_cast<uint32_t *>(p + at); at += up256((size_t)F1 * 3 * 4);
     w.first = reinterpret_cast<uint8_t *>(p + at); at += up256((size_t)F1 * 3);
     w.pos = reinterpret_cast<int32_t *>(p + at); at += up256((size_t)F1 * 3 * 4);
     w.foff = reinterpret_cast<int32_t *>(p + at); at += up256((size_t)F1 * 4);
     w.virr = reinterpret_cast<int32_t *>(p + at); at += up256((size_t)V * 4);
     w.bsum = reinterpret_cast<int32_t *>(p + at); at += scan_bytes(F1 * 3);
-    w.t.mask = (u64)(w.slots - 1);
-    w.t.shift = 64;
-    for (int64_t s = w.slots; s > 1; s >>= 1) --w.t.shift;        // slots = 2^(64 - shift)
     w.bytes = at;
     return w;
 }
@@ -457,9 +397,7 @@ void emit_launch(const T *verts, int64_t V, const int32_t *faces, int64_t F, int
         hipLaunchKernelGGL(even_kernel<T>, dim3(blocks_of(V, MT_THREADS)), block, 0, st, verts, (int)V, offsets, neighbors, boundary_edge, boundary_vertex,
                            (int)nnz, (const int32_t *)w.virr, out_verts);
     } else {
-        const int64_t words = V * 3 * (int64_t)(sizeof(T) / 4);
-        hipLaunchKernelGGL(copy_words_kernel, dim3(blocks_of(words, MT_THREADS)), block, 0, st, reinterpret_cast<const uint32_t *>(verts), words,
-                           reinterpret_cast<uint32_t *>(out_verts));
+        copy_words(verts, (size_t)V * 3 * sizeof(T), out_verts, st);
     }
     hipLaunchKernelGGL(faces_kernel<T>, dim3(blocks_of(F, MT_THREADS)), block, 0, st, verts, faces, (int)F, (int)V, w.t, (const int32_t *)w.foff,
                        (int)n_marked, (int)n_out, out_faces, face_parent);
@@ -495,12 +433,11 @@ int vt_mesh_subdivide_count(const void *verts, int verts_f64, int64_t V, const i
     hipStream_t st = (hipStream_t)stream;
     const SubWs w = sub_ws(workspace, V, F);
     int rc = vt_fill32(w.status, 0u, MT_STATUS_BYTES, st);
-    if (!rc) rc = vt_fill32(w.t.keys, 0xffffffffu, (size_t)w.slots * 8, st);
-    if (!rc) rc = vt_fill32(w.t.vals, 0u, (size_t)w.slots * 8, st);
-    if (!rc) rc = vt_fill32(w.t.minh, 0x7fffffffu, (size_t)w.slots * 4, st);
-    if (!rc) rc = vt_fill32(w.t.maxh, 0xffffffffu, (size_t)w.slots * 4, st);
-    if (!rc) rc = vt_fill32(w.t.eid, 0xffffffffu, (size_t)w.slots * 4, st);
-    if (!rc) rc = vt_fill32(w.t.emark, 0u, (size_t)w.slots * 4, st);
+    if (!rc) rc = edge_table_clear(w.t.e, st);
+    if (!rc) rc = vt_fill32(w.t.minh, 0x7fffffffu, (size_t)w.t.e.slots * 4, st);
+    if (!rc) rc = vt_fill32(w.t.maxh, 0xffffffffu, (size_t)w.t.e.slots * 4, st);
+    if (!rc) rc = vt_fill32(w.t.eid, 0xffffffffu, (size_t)w.t.e.slots * 4, st);
+    if (!rc) rc = vt_fill32(w.t.emark, 0u, (size_t)w.t.e.slots * 4, st);
     if (rc) return rc;
     const dim3 block(MT_THREADS), fgrid(blocks_of(F, MT_THREADS)), hgrid(blocks_of(F * 3, MT_THREADS));
     const double max2 = max_edge * max_edge;
@@ -511,17 +448,11 @@ int vt_mesh_subdivide_count(const void *verts, int verts_f64, int64_t V, const i
         hipLaunchKernelGGL(first_kernel<float>, hgrid, block, 0, st, static_cast<const float *>(verts), F * 3, mark, max2, w.t, w.first);
     scan_launch(ByteFlag{w.first}, F * 3, w.bsum, w.pos, w.status + ST_NMARKED, st);
     hipLaunchKernelGGL(number_kernel, hgrid, block, 0, st, F * 3, (const uint8_t *)w.first, (const int32_t *)w.pos, w.t, w.status);
-    const ChildrenFn fn{w.t.he_slot, w.t.eid};
-    const unsigned nb = blocks_of(F, MT_CHUNK);
-    hipLaunchKernelGGL(iscan_count_kernel, dim3(nb), block, 0, st, fn, F, w.bsum);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), block, 0, st, w.bsum, (int)nb, w.status + ST_NOUT);
-    hipLaunchKernelGGL(iscan_write_kernel, dim3(nb), block, 0, st, fn, F, (const int32_t *)w.bsum, w.foff);
+    scan_launch(ChildrenFn{w.t.he_slot, w.t.eid}, F, w.bsum, w.foff, w.status + ST_NOUT, st);
     rc = vt_check(hipGetLastError(), "vt_mesh_subdivide_count");
     if (rc) return rc;
     int32_t h[16];
-    hipError_t e = hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    rc = vt_check(e, "vt_mesh_subdivide_count");
+    rc = read_status(workspace, h, st, "vt_mesh_subdivide_count");
     if (rc) return rc;
     if (h[ST_BAD]) return vt_fail(VT_ERR_INVALID, "vt_mesh_subdivide_count: a face has an index outside [0, V) or a repeated index");
     if (h[ST_NMARKED] < 0 || h[ST_NMARKED] > 3 * F || h[ST_NOUT] < F || h[ST_NOUT] > 4 * F || V + (int64_t)h[ST_NMARKED] > 0x7fffffff)
@@ -546,9 +477,7 @@ int vt_mesh_subdivide_emit(const void *verts, int verts_f64, int64_t V, const in
         return vt_fail(VT_ERR_INVALID, "vt_mesh_subdivide_emit: scheme 1 goes with mark 0 only");
     hipStream_t st = (hipStream_t)stream;
     if (F == 0) {                                                  // nothing to split: the vertices' bits
-        const int64_t words = V * 3 * (verts_f64 ? 2 : 1);
-        hipLaunchKernelGGL(copy_words_kernel, dim3(blocks_of(words, MT_THREADS)), dim3(MT_THREADS), 0, st, static_cast<const uint32_t *>(verts), words,
-                           static_cast<uint32_t *>(out_verts));
+        copy_words(verts, (size_t)V * 3 * (verts_f64 ? 8 : 4), out_verts, st);
         return vt_check(hipGetLastError(), "vt_mesh_subdivide_emit");
     }
     if (!workspace || workspace_bytes < sub_ws(nullptr, V, F).bytes) return vt_fail(VT_ERR_WORKSPACE, "vt_mesh_subdivide_emit");

@@ -16,9 +16,8 @@
 //                 nearest).  Integer addition is associative, so the sums carry no trace of the order: equal bits from run to run with
 //                 no float atomic and no sort.  A term's error is at most 2^-62 of the component's largest term.
 //                 bbox: atomicMin / atomicMax on an order-preserving integer image of the float64 coordinate.
-//   edges         an open-addressing table of 64-bit keys (lo << 32 | hi), 4 F slots rounded up to a power of two (at most 3 F keys:
-//                 never full), claimed by atomicCAS; the value counts the faces that run lo -> hi in its low word and hi -> lo in its
-//                 high word by one 64-bit integer add.  A second pass classifies the occupied slots.
+//   edges         mesh_edges.h's table: per undirected edge the faces that run lo -> hi and hi -> lo.  A second pass classifies the
+//                 occupied slots.
 //   filter        two exclusive scans (kept vertices, kept faces), then the copies; order is preserved.
 // Every per-component atomic is issued once per (wave, component): lanes of a wave that hold the same component combine first.
 // A face with an index outside [0, V) is never dereferenced; it takes no part and sets bit 0 of the status word.
@@ -28,6 +27,7 @@
 #include <type_traits>
 
 #include "mesh_common.h"
+#include "mesh_edges.h"
 #include "vt_common.h"
 #include "vtaco_hip.h"
 
@@ -266,36 +266,6 @@ void stats_launch(const T *verts, int V, const int32_t *faces, int F, const int3
 }
 
 // ---- edges ------------------------------------------------------------------------------------------------------------------------------------
-constexpr u64 EDGE_EMPTY = ~0ull;
-
-int64_t edge_slots(int64_t F) {
-    int64_t cap = 1024;
-    while (cap < 4 * F) cap <<= 1;
-    return cap;
-}
-
-__device__ inline void edge_insert(u64 *keys, u64 *vals, u64 mask, int shift, int a, int b) {
-    if (a == b) return;
-    const u64 key = a < b ? ((u64)(unsigned)a << 32 | (unsigned)b) : ((u64)(unsigned)b << 32 | (unsigned)a);
-    const u64 inc = a < b ? 1ull : (1ull << 32);
-    u64 slot = (key * 0x9E3779B97F4A7C15ull) >> shift;
-    for (u64 probes = 0; probes <= mask; ++probes) {          // (at most 3 F of the >= 4 F slots are ever claimed: a free one is met)
-        const u64 old = atomicCAS(keys + slot, EDGE_EMPTY, key);
-        if (old == EDGE_EMPTY || old == key) { atomicAdd(vals + slot, inc); return; }
-        slot = (slot + 1) & mask;
-    }
-}
-
-__global__ void __launch_bounds__(MT_THREADS) edge_insert_kernel(const int32_t *faces, int F, int V, u64 *keys, u64 *vals, u64 mask, int shift) {
-    __shared__ int32_t lds[MT_THREADS * 3];
-    int f, a, b, c;
-    bool ok;
-    if (!load_face(faces, F, V, lds, f, a, b, c, ok) || !ok) return;
-    edge_insert(keys, vals, mask, shift, a, b);
-    edge_insert(keys, vals, mask, shift, b, c);
-    edge_insert(keys, vals, mask, shift, c, a);
-}
-
 // out: [4][C] int32 -- n_edges, n_boundary, n_nonmanifold, n_misoriented
 __global__ void __launch_bounds__(MT_THREADS)
 edge_count_kernel(const u64 *keys, const u64 *vals, int64_t slots, const int32_t *comp_of_vertex, int V, int C, int32_t *n_edges, int32_t *n_boundary,
@@ -383,13 +353,6 @@ void filter_launch(const T *verts, int V, const int32_t *faces, int F, const int
 }
 
 bool sizes_ok(int64_t V, int64_t F) { return V >= 1 && F >= 1 && V <= MT_MAX_V && F <= MT_MAX_F; }
-
-// the status words to the host: one copy, one wait
-int read_status(const void *workspace, int32_t (&h)[16], hipStream_t st, const char *where) {
-    hipError_t e = hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return vt_check(e, where);
-}
 
 size_t table_bytes(int64_t V) { return MT_STATUS_BYTES + 2 * up256((size_t)V * sizeof(int32_t)) + scan_bytes(V); }
 size_t filter_bytes(int64_t V, int64_t F) { return MT_STATUS_BYTES + up256((size_t)F * sizeof(int32_t)) + scan_bytes(V > F ? V : F); }
@@ -488,19 +451,16 @@ int vt_mesh_edge_stats(const int32_t *faces, int64_t F, int64_t V, const int32_t
                        int32_t *n_nonmanifold, int32_t *n_misoriented, void *workspace, size_t workspace_bytes, void *stream) {
     if (!sizes_ok(V, F) || C < 1 || C > V || !faces || !comp_of_vertex || !n_edges || !n_boundary || !n_nonmanifold || !n_misoriented)
         return vt_fail(VT_ERR_INVALID, "vt_mesh_edge_stats: bad argument (V >= 1, F >= 1, 1 <= C <= V)");
-    const int64_t slots = edge_slots(F);
-    if (!workspace || workspace_bytes < (size_t)slots * 16) return vt_fail(VT_ERR_WORKSPACE, "vt_mesh_edge_stats");
+    const EdgeTable t = edge_table_at(workspace, F);
+    if (!workspace || workspace_bytes < (size_t)t.slots * 16) return vt_fail(VT_ERR_WORKSPACE, "vt_mesh_edge_stats");
     hipStream_t st = (hipStream_t)stream;
-    u64 *keys = static_cast<u64 *>(workspace), *vals = keys + slots;
-    int shift = 64;
-    for (int64_t s = slots; s > 1; s >>= 1) --shift;              // slots = 2^(64 - shift)
-    int rc = vt_fill32(keys, 0xffffffffu, (size_t)slots * 8, st);
-    if (!rc) rc = vt_fill32(vals, 0u, (size_t)slots * 8, st);
+    int rc = edge_table_clear(t, st);
     int32_t *outs[4] = {n_edges, n_boundary, n_nonmanifold, n_misoriented};
     for (int k = 0; k < 4 && !rc; ++k) rc = vt_fill32(outs[k], 0u, (size_t)C * 4, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(edge_insert_kernel, dim3(blocks_of(F, MT_THREADS)), dim3(MT_THREADS), 0, st, faces, (int)F, (int)V, keys, vals, (u64)(slots - 1), shift);
-    hipLaunchKernelGGL(edge_count_kernel, dim3(blocks_of(slots, MT_THREADS)), dim3(MT_THREADS), 0, st, (const u64 *)keys, (const u64 *)vals, slots,
+    // (this workspace has no status words: a face with an index outside [0, V) takes no part and is not reported)
+    hipLaunchKernelGGL(edge_insert_kernel<false>, dim3(blocks_of(F, MT_THREADS)), dim3(MT_THREADS), 0, st, faces, (int)F, (int)V, t, (int32_t *)nullptr);
+    hipLaunchKernelGGL(edge_count_kernel, dim3(blocks_of(t.slots, MT_THREADS)), dim3(MT_THREADS), 0, st, (const u64 *)t.keys, (const u64 *)t.vals, t.slots,
                        comp_of_vertex, (int)V, (int)C, n_edges, n_boundary, n_nonmanifold, n_misoriented);
     return vt_check(hipGetLastError(), "vt_mesh_edge_stats");
 }
