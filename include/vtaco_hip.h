@@ -1710,6 +1710,26 @@ int vt_mesh_cluster_place(const void *verts, int verts_f64, int64_t V, const int
                           const int32_t *cluster_rep, int64_t K, int placement, void *out_verts, int32_t *state, void *workspace, size_t workspace_bytes,
                           void *stream);
 
+/* ---- mesh decimation by edge collapse (mesh_collapse.hip) --------------------------------------------------------------------------- */
+/* Replaces: the reference's generation.simplify_nfaces as its tool chain means it (simplify_mesh: quadric edge-collapse decimation).    */
+/*   Rounds of independent collapses: an edge {u, v}, u < v, is a candidate when neither end touches an edge that is not used once in     */
+/*   each direction, the ends share exactly two neighbours, the link is no tetrahedron, the position and cost are finite and no face     */
+/*   around it flips; of the candidates an independent set is taken by a key (12 bits of the float32 cost, 20 hash bits, the edge's       */
+/*   lowest half-edge) that has to be the smallest within both ends' closed one-rings; of those the first ceil((F - target) / 2) by       */
+/*   lowest half-edge are applied, each removing two faces.  A closed manifold stays one and lands on the largest even count <=           */
+/*   target_faces; boundary and non-manifold edges never move.  tests/mesh_collapse_ref.py is the definition and the kernels equal it     */
+/*   bit for bit ("mesh_collapse.hip").  Meshes and size rules as in the topology block; F <= (2^31 - 1) / 6.                  */
+/* vt_mesh_collapse: placement 0 ('optimal': the minimiser of the summed quadrics about the midpoint, the midpoint where that is not      */
+/*   finite or not better) or 1 ('midpoint'); max_rounds >= 1 bounds the rounds that collapse something.  out_verts (capacity V, the      */
+/*   vertices' type), out_faces (capacity F), vertex_map [V] (the output vertex every input vertex went into; -1: unreferenced);          */
+/*   *rounds counts the rounds that collapsed something, *stalled is 1 when a round found no candidate above the target.  Waits for       */
+/*   the stream: one read after the prologue (a face index outside [0, V) or a non-finite referenced coordinate: VT_ERR_INVALID, before   */
+/*   any such index is dereferenced), one per batch of 4 rounds, one at the end.                                                          */
+size_t vt_mesh_collapse_workspace_bytes(int64_t V, int64_t F);
+int vt_mesh_collapse(const void *verts, int verts_f64, int64_t V, const int32_t *faces, int64_t F, int64_t target_faces, int placement, int max_rounds,
+                     void *out_verts, int32_t *out_faces, int32_t *vertex_map, int *n_out_verts, int *n_out_faces, int *rounds, int *stalled,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- mesh normals (mesh_normals.hip) ----------------------------------------------------------------------------------------------- */
 /* Replaces: trimesh.Trimesh.face_normals / .vertex_normals of the meshes the reference builds (src/conv_onet/generation.py:273-284;     */
 /*   Generator3D's with_normals, generation.py:34,46).  tests/mesh_normals_ref.py restates the rule in numpy float64.                    */

@@ -453,6 +453,8 @@ SIGNATURES = {
     "vt_mesh_cluster_faces": (_I, [_VP, _I64, _I64, _VP, _I, _VP, _VP, _IP, _IP, _VP, _SZ, _VP]),
     "vt_mesh_cluster_place_workspace_bytes": (_SZ, [_I64]),
     "vt_mesh_cluster_place": (_I, [_VP, _I, _I64, _VP, _I64, _I, _VP, _VP, _I64, _I, _VP, _VP, _VP, _SZ, _VP]),
+    "vt_mesh_collapse_workspace_bytes": (_SZ, [_I64, _I64]),
+    "vt_mesh_collapse": (_I, [_VP, _I, _I64, _VP, _I64, _I64, _I, _I, _VP, _VP, _VP, _IP, _IP, _IP, _IP, _VP, _SZ, _VP]),   # simplify_mesh (edge collapse)
     "vt_mesh_normals_workspace_bytes": (_SZ, [_I64, _I64]),
     "vt_mesh_normals": (_I, [_VP, _I, _I64, _VP, _I64, _I, _VP, _VP, _VP, _SZ, _VP]),                   # trimesh face_normals / vertex_normals
     "vt_mesh_boundary_workspace_bytes": (_SZ, [_I64, _I64]),

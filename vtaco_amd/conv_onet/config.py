@@ -73,6 +73,8 @@ def get_generator(model, cfg, device, **kwargs):
                       fill_holes_max_edges=g.get('fill_holes_max_edges'), smooth=g.get('smooth'),
                       smooth_iterations=g.get('smooth_iterations', 10))
     # (a method, not a constructor argument: the constructor's parameter list is pinned)
+    if 'simplify_method' in g:                                      # (absent: the default, vertex clustering, with nothing called)
+        gen.configure_simplify(g['simplify_method'])
     return gen.configure_subdivide(g.get('subdivide'), iterations=g.get('subdivide_iterations', 1), max_edge=g.get('subdivide_max_edge'))
 
 

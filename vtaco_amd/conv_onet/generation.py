@@ -116,6 +116,16 @@ class Mesh(namedtuple("Mesh", ["vertices", "faces"])):
         from ..utils import mesh_clean
         return mesh_clean.simplify_report(self, nfaces=nfaces, resolution=resolution, placement=placement)
 
+    def decimate(self, nfaces, placement="optimal"):
+        """At most ``nfaces`` faces by quadric edge collapses that keep a manifold a manifold (utils/mesh_clean.py: decimate)."""
+        from ..utils import mesh_clean
+        return mesh_clean.decimate(self, nfaces, placement=placement)
+
+    def decimate_report(self, nfaces, placement="optimal"):
+        """(mesh, DecimateReport) (utils/mesh_clean.py: decimate_report)."""
+        from ..utils import mesh_clean
+        return mesh_clean.decimate_report(self, nfaces, placement=placement)
+
     def merge_vertices(self, tol=0.0, unique_faces=False):
         """Equal vertices merged (within ``tol`` of a lattice where ``tol`` > 0), collapsed faces and unreferenced vertices dropped."""
         from ..utils import mesh_clean
@@ -398,6 +408,14 @@ class Generator3D(object):
     most N faces but is not the finest such grid, and its topology is not the input's (``Mesh.components()`` reports what it is).
     ``None`` (the default) launches nothing.  The Inferencer does not apply it; generate_obj_mesh_sharded refuses it (VtError).
 
+    ``configure_simplify(method)`` (config ``generation.simplify_method``; a method, not a constructor argument, as
+    ``configure_subdivide`` is): ``'cluster'`` (the default state) is the vertex clustering above, with not one launch more than
+    before; ``'collapse'`` runs ``Mesh.decimate(nfaces=N)`` in its place -- rounds of independent quadric edge collapses,
+    utils/mesh_clean.py, csrc/mesh_collapse.hip -- which keeps a closed manifold closed with its Euler number and lands on the largest
+    even count <= N (boundary and non-manifold edges never move; where nothing more can collapse the result has more than N faces).
+    It costs one host read per four rounds, tens of rounds of some twenty launches.  With ``with_normals`` the normals are recomputed
+    from the geometry, as after clustering.  Any other value raises VtError; generate_obj_mesh_sharded refuses ``'collapse'``.
+
     ``fill_holes`` / ``fill_holes_max_edges`` (config ``generation.fill_holes`` / ``generation.fill_holes_max_edges``): ``'fan'`` or
     ``'centroid'`` caps the boundary loops of the finished object mesh -- ``Mesh.fill_holes(method, max_edges)``, utils/mesh_clean.py,
     csrc/mesh_fill.hip -- after the component filter (a dropped floater's holes are not worth closing) and before ``simplify_nfaces``
@@ -457,6 +475,9 @@ class Generator3D(object):
     SUBDIVIDE = (None, "midpoint", "loop")
     # configure_subdivide's state; the class attributes are the default: nothing runs
     subdivide, subdivide_iterations, subdivide_max_edge = None, 1, None
+    SIMPLIFY_METHODS = ("cluster", "collapse")
+    # configure_simplify's state; the class attribute is the default: vertex clustering
+    simplify_method = "cluster"
 
     MAX_SCENE_GRAPHS = 4
     FUSED_CHUNKS_PER_CALL = 256          # attention_local: chunks of points_batch_size points evaluated per launch sequence (see _fused_chunks_per_call)
@@ -547,6 +568,13 @@ class Generator3D(object):
                 raise VtError(f"Generator3D.configure_subdivide: max_edge goes with scheme='midpoint' (got {scheme!r})")
         self.subdivide, self.subdivide_iterations = scheme, int(iterations)
         self.subdivide_max_edge = None if max_edge is None else float(max_edge)
+        return self
+
+    def configure_simplify(self, method="cluster"):
+        """How ``simplify_nfaces`` is met in ``_clean`` (the class docstring): ``'cluster'`` or ``'collapse'``.  Returns self."""
+        if method not in self.SIMPLIFY_METHODS:
+            raise VtError(f"Generator3D.configure_simplify: method must be one of {self.SIMPLIFY_METHODS} (got {method!r})")
+        self.simplify_method = method
         return self
 
     def _subdivided(self, mesh):
@@ -867,9 +895,12 @@ class Generator3D(object):
         if self.simplify_nfaces is None or mesh.faces.shape[0] <= self.simplify_nfaces:
             return mesh
         from ..utils import mesh_clean
-        simplified = mesh_clean.simplify(mesh, nfaces=self.simplify_nfaces)
+        if self.simplify_method == "collapse":
+            simplified = mesh_clean.decimate(mesh, self.simplify_nfaces)
+        else:
+            simplified = mesh_clean.simplify(mesh, nfaces=self.simplify_nfaces)
         if isinstance(mesh, NormalMesh) and simplified.faces.shape[0] > 0:
-            # clustering moves the vertices: marching cubes' normals no longer belong to them -- recomputed from the geometry
+            # both methods move the vertices: marching cubes' normals no longer belong to them -- recomputed from the geometry
             return mesh_clean.with_vertex_normals(simplified, weight="area")
         return simplified
 
@@ -926,6 +957,9 @@ class Generator3D(object):
         if self.with_normals:
             raise VtError("generate_obj_mesh_sharded: with_normals is not built for the sharded route; take the normals of the returned "
                           "mesh with Mesh.with_vertex_normals(), or ops.mc.marching_cubes_normals of the gathered value grid")
+        if self.simplify_method != "cluster":
+            raise VtError("generate_obj_mesh_sharded: simplify_method='collapse' (configure_simplify) is not built for the sharded route; "
+                          "decimate the returned mesh with Mesh.decimate(nfaces)")
         if self.simplify_nfaces is not None:
             raise VtError("generate_obj_mesh_sharded: simplify_nfaces is not built for the sharded route; simplify the returned mesh with "
                           "Mesh.simplify(nfaces=...)")

@@ -1,4 +1,5 @@
-// The undirected-edge hash table of mesh_topo.hip, mesh_fill.hip, mesh_smooth.hip and mesh_subdivide.hip (DESIGN.md, section "mesh_edges.h").
+// The undirected-edge hash table of mesh_topo.hip, mesh_fill.hip, mesh_smooth.hip, mesh_subdivide.hip and mesh_collapse.hip (DESIGN.md, section
+// "mesh_edges.h").
 // Open addressing over 64-bit keys (lo << 32 | hi), 4 F slots rounded up to a power of two (at most 3 F keys: never full), claimed by
 // atomicCAS.  The value counts the faces that run lo -> hi in its low word and hi -> lo in its high word by one 64-bit integer add; the
 // halves cannot carry into each other (3 F < 2^32).  In a workspace the table is slots * 16 bytes: the keys, then the values.

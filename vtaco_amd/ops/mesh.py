@@ -1,6 +1,6 @@
 """Topology of a triangle mesh (vt_mesh_components, vt_mesh_component_table, vt_mesh_component_stats, vt_mesh_edge_stats, vt_mesh_filter:
 csrc/mesh_topo.hip), its normals (vt_mesh_normals: csrc/mesh_normals.hip; ``ops.mesh.normals``) and, at the end of the file, its simplification and welding (vt_mesh_cluster, vt_mesh_weld, vt_mesh_cluster_faces,
-vt_mesh_cluster_place: csrc/mesh_simplify.hip), and behind those its hole filling (vt_mesh_boundary, vt_mesh_boundary_loops, vt_mesh_fill_count,
+vt_mesh_cluster_place: csrc/mesh_simplify.hip; vt_mesh_collapse: csrc/mesh_collapse.hip, ``ops.mesh.collapse``), and behind those its hole filling (vt_mesh_boundary, vt_mesh_boundary_loops, vt_mesh_fill_count,
 vt_mesh_fill_emit: csrc/mesh_fill.hip; ``ops.mesh.boundary_loops``, ``ops.mesh.fill_holes``), and last its vertex adjacency and smoothing (vt_mesh_adjacency_count, vt_mesh_adjacency_fill, vt_mesh_smooth_weights,
 vt_mesh_smooth: csrc/mesh_smooth.hip; ``ops.mesh.vertex_adjacency``, ``ops.mesh.smooth``), and its subdivision (vt_mesh_subdivide_count, vt_mesh_subdivide_emit, vt_mesh_subdivide_midpoints, vt_mesh_subdivide_bwd: csrc/mesh_subdivide.hip; ``ops.mesh.subdivide``, ``ops.mesh.subdivide_backward``); those three families alone take F = 0.  A submodule only: callers write ``ops.mesh.components``, ``ops.mesh.component_table``, ``ops.mesh.component_stats``,
 ``ops.mesh.edge_stats``, ``ops.mesh.filter_components``.  faces are int32 [F,3] and vertices float32 or float64 [V,3] device tensors, as
@@ -283,6 +283,55 @@ def cluster_place(vertices, faces, clusters, n_clusters, placement="quadric"):
                                     PLACEMENTS.index(placement), dev_ptr(out, "out_vertices", out.dtype), dev_ptr(state, "state", I32),
                                     ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "vt_mesh_cluster_place")
     return out
+
+
+# ---- decimation by edge collapse (csrc/mesh_collapse.hip; tests/mesh_collapse_ref.py is the definition) ----------------------------------
+Collapsed = namedtuple("Collapsed", ["vertices", "faces", "vertex_map", "rounds", "stalled"])
+COLLAPSE_PLACEMENTS = ("optimal", "midpoint")
+MAX_COLLAPSE_FACES = (2 ** 31 - 1) // 6
+
+
+def collapse(vertices, faces, nfaces, placement="optimal", max_rounds=None):
+    """Collapsed(vertices, faces, vertex_map int32 [V], rounds, stalled): the mesh decimated to at most ``nfaces`` faces by rounds of
+    independent quadric edge collapses (vt_mesh_collapse).  An edge may collapse when neither end touches a boundary or non-manifold
+    edge, its ends share exactly two neighbours (and the link is no tetrahedron) and no face around it flips, so a closed manifold stays
+    one, with its Euler number, and lands on the largest even count <= ``nfaces``; ``stalled`` tells that a round found nothing left
+    to collapse above that.  ``'optimal'`` puts the merged vertex at the minimiser of the summed quadrics (the midpoint where that is
+    not finite or not better), ``'midpoint'`` at the midpoint.  ``max_rounds`` bounds the rounds that collapse something (None: no
+    bound); ``rounds`` is their number.  ``vertex_map[v]`` is the output vertex that input vertex v went into, -1 for a vertex no face
+    references.  Deterministic, bit for bit.  One host read per four rounds and two more; a mesh that has at most ``nfaces`` faces
+    comes back as the same tensors with nothing launched (vertex_map None).  ``vertices`` and ``faces`` are slices of capacity
+    (V, F) buffers where the result has more than half the input's rows, copies otherwise; ``vertex_map`` is [V] by its meaning."""
+    what = "mesh.collapse"
+    if placement not in COLLAPSE_PLACEMENTS:
+        raise VtError(f"{what}: placement must be one of {COLLAPSE_PLACEMENTS} (got {placement!r})")
+    if isinstance(nfaces, bool) or not isinstance(nfaces, numbers.Integral) or nfaces < 1:
+        raise VtError(f"{what}: nfaces must be a positive integer (got {nfaces!r})")
+    if max_rounds is not None and (isinstance(max_rounds, bool) or not isinstance(max_rounds, numbers.Integral) or not 1 <= max_rounds < 2 ** 31):
+        raise VtError(f"{what}: max_rounds must be None or an integer in [1, 2^31) (got {max_rounds!r})")
+    given = (vertices, faces)
+    faces = _faces(what, faces, vertices)
+    vertices = _vertices(what, vertices)
+    V, F, dev = vertices.shape[0], faces.shape[0], faces.device
+    if F <= nfaces:
+        return Collapsed(*given, None, 0, False)
+    if F > MAX_COLLAPSE_FACES:
+        raise VtError(f"{what}: F = {F} is above {MAX_COLLAPSE_FACES} = (2^31 - 1) / 6")
+    out_v = torch.empty((V, 3), dtype=vertices.dtype, device=dev)
+    out_f = torch.empty((F, 3), dtype=I32, device=dev)
+    vmap = torch.empty(V, dtype=I32, device=dev)
+    lib = _lib.load()
+    ws = _ws(lib.vt_mesh_collapse_workspace_bytes(V, F), dev)
+    nv, nf, rounds, stalled = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.vt_mesh_collapse(dev_ptr(vertices, "vertices", vertices.dtype), int(vertices.dtype == F64), V, dev_ptr(faces, "faces", I32), F,
+                               int(nfaces), COLLAPSE_PLACEMENTS.index(placement), 2 ** 31 - 1 if max_rounds is None else int(max_rounds),
+                               dev_ptr(out_v, "out_vertices", out_v.dtype), dev_ptr(out_f, "out_faces", I32), dev_ptr(vmap, "vertex_map", I32),
+                               ctypes.byref(nv), ctypes.byref(nf), ctypes.byref(rounds), ctypes.byref(stalled), ctypes.c_void_p(ws.data_ptr()),
+                               ws.numel() * 8, stream_ptr()), "vt_mesh_collapse")
+    # the kernel needs capacity (V, F); a result of at most half of that is copied out, so it does not keep the large buffers alive
+    vertices, faces = out_v[:nv.value], out_f[:nf.value]
+    return Collapsed(vertices.clone() if 2 * nv.value <= V else vertices, faces.clone() if 2 * nf.value <= F else faces, vmap, rounds.value,
+                     bool(stalled.value))
 
 
 # ---- hole filling (csrc/mesh_fill.hip; tests/mesh_fill_ref.py is the definition) ----------------------------------------------------------

@@ -9,6 +9,8 @@ its meshes in ``trimesh.Trimesh`` (``split``, ``area``, ``volume``, ``is_waterti
     simplify(mesh, nfaces=None, resolution=None, placement='quadric') -> Mesh        (csrc/mesh_simplify.hip, as the next two)
     simplify_report(...) -> (Mesh, SimplifyReport)
     merge_vertices(mesh, tol=0.0, unique_faces=False) -> Mesh
+    decimate(mesh, nfaces, placement='optimal') -> Mesh          manifold-preserving edge collapse (csrc/mesh_collapse.hip, as the next)
+    decimate_report(...) -> (Mesh, DecimateReport)
     face_normals(mesh) -> [F,3]                  unit, (0,0,0) for a degenerate face (csrc/mesh_normals.hip, as the next two)
     vertex_normals(mesh, weight='area') -> [V,3] 'area' or 'angle'; (0,0,0) for a vertex no live face references
     with_vertex_normals(mesh, weight='area') -> NormalMesh
@@ -247,6 +249,42 @@ def merge_vertices(mesh, tol=0.0, unique_faces=False):
     if faces.n_clusters == 0:
         return _empty(v, f)
     return Mesh(m.cluster_place(v, f, clusters, faces.n_clusters, "representative"), faces.faces)
+
+
+# ---- decimation by edge collapse (csrc/mesh_collapse.hip; tests/mesh_collapse_ref.py is the definition) -------------------------------
+DecimateReport = namedtuple("DecimateReport", ["rounds", "stalled", "vertex_map"])
+DecimateReport.__doc__ = """rounds: the rounds that collapsed at least one edge (0: the mesh was returned unchanged); stalled: a round found
+no edge left that may collapse, so the result has more than ``nfaces`` faces; vertex_map int32 [V]: the output vertex every input vertex
+went into (-1: unreferenced; None where nothing ran)."""
+
+
+def decimate_report(mesh, nfaces, placement="optimal"):
+    """(Mesh, DecimateReport).  Quadric edge-collapse decimation in rounds of independent collapses (``ops.mesh.collapse``): what the
+    reference's ``simplify_nfaces`` means.  Unlike ``simplify`` it keeps the surface what it is -- a closed oriented manifold stays one,
+    with its components and Euler number -- and lands on the largest even face count <= ``nfaces``.  Boundary edges and non-manifold
+    edges never move, and neither do their ends, so an open mesh keeps its rim vertex for vertex and may stall above ``nfaces``.
+    ``placement='optimal'`` puts a merged vertex where the summed squared distances to the planes of both ends' faces are smallest,
+    ``'midpoint'`` at the middle of the edge.  A mesh with at most ``nfaces`` faces is returned itself, with nothing launched.  A
+    ``NormalMesh`` gets geometric normals afterwards, as after ``simplify``.  Deterministic, bit for bit."""
+    from .. import ops
+    from ..conv_onet.generation import Mesh, NormalMesh
+    what = "mesh_clean.decimate"
+    nfaces = _positive_int(what, "nfaces", nfaces)
+    if placement not in ops.mesh.COLLAPSE_PLACEMENTS:
+        raise VtError(f"{what}: placement must be one of {ops.mesh.COLLAPSE_PLACEMENTS} (got {placement!r})")
+    v, f = _parts(mesh)
+    if f.shape[0] <= nfaces:
+        return (mesh if isinstance(mesh, Mesh) else Mesh(v, f)), DecimateReport(0, False, None)
+    out = ops.mesh.collapse(v, f, nfaces, placement=placement)
+    result = Mesh(out.vertices, out.faces)
+    if isinstance(mesh, NormalMesh) and out.faces.shape[0] > 0:
+        result = with_vertex_normals(result, weight="area")
+    return result, DecimateReport(out.rounds, out.stalled, out.vertex_map)
+
+
+def decimate(mesh, nfaces, placement="optimal"):
+    """``decimate_report`` without the report."""
+    return decimate_report(mesh, nfaces, placement=placement)[0]
 
 
 # ---- normals (csrc/mesh_normals.hip; tests/mesh_normals_ref.py is the definition) --------------------------------------------------------
