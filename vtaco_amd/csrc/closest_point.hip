@@ -110,7 +110,7 @@ closest_point_slab_kernel(int F, const CpScene *scenes, int max_F, const float *
         __syncthreads();
         for (int j = 0; j < cnt; ++j) {
             const double *r = lds + j * CP_REC;
-            if (r[12] == 2.0) continue;
+            if (r[CP_KIND] == CP_SKIP) continue;
             double q[3];
             const double d = cp_face(r, px, py, pz, q);
             if (d < best) { best = d; best_f = f0 + j; }

@@ -7,11 +7,13 @@
 #include <stdint.h>
 
 constexpr int CP_REC = 14;                      // doubles per face record (112 bytes: 16-byte aligned rows): a, ab, ac, d00, d01, d11, kind, 0
+constexpr int CP_KIND = 12;                     // the record's kind slot: 0 regular, 1 degenerate, CP_SKIP
+constexpr double CP_SKIP = 2.0;                 // the kind of a face with an index outside [0, V): never dereferenced, met by no query
 constexpr int CP_BAD_INDEX = 1;                 // status bits
 constexpr int CP_BAD_SCENE = 2;
 
-// the record of face f: kind (rec[12]) 0 regular, 1 degenerate (ab x ac is exactly zero), 2 skipped (an index outside [0, V): never
-// dereferenced).  false for kind 2: the caller reports it
+// the record of face f: kind (rec[CP_KIND]) 0 regular, 1 degenerate (ab x ac is exactly zero), CP_SKIP (an index outside [0, V)).
+// false for CP_SKIP: the caller reports it
 __device__ inline bool cp_fill_record(const float *verts, int V, const int32_t *faces, size_t f, double *rec) {
     int idx[3];
     bool ok = true;
@@ -22,7 +24,7 @@ __device__ inline bool cp_fill_record(const float *verts, int V, const int32_t *
     }
     if (!ok) {
 #pragma unroll
-        for (int k = 0; k < CP_REC; ++k) rec[k] = k == 12 ? 2.0 : 0.0;
+        for (int k = 0; k < CP_REC; ++k) rec[k] = k == CP_KIND ? CP_SKIP : 0.0;
         return false;
     }
     double p[3][3];
@@ -39,7 +41,7 @@ __device__ inline bool cp_fill_record(const float *verts, int V, const int32_t *
     rec[9] = (abx * abx + aby * aby) + abz * abz;
     rec[10] = (abx * acx + aby * acy) + abz * acz;
     rec[11] = (acx * acx + acy * acy) + acz * acz;
-    rec[12] = (nx == 0.0 && ny == 0.0 && nz == 0.0) ? 1.0 : 0.0;
+    rec[CP_KIND] = (nx == 0.0 && ny == 0.0 && nz == 0.0) ? 1.0 : 0.0;
     rec[13] = 0.0;
     return true;
 }
@@ -61,7 +63,7 @@ __device__ inline double cp_face(const double *r, double px, double py, double p
     const double apx = px - ax, apy = py - ay, apz = pz - az;
     const double d1 = (abx * apx + aby * apy) + abz * apz;
     const double d2 = (acx * apx + acy * apy) + acz * apz;
-    if (r[12] != 0.0) {                           // degenerate: the nearest of the edges ab, ac, bc (the first among equals)
+    if (r[CP_KIND] != 0.0) {                           // degenerate: the nearest of the edges ab, ac, bc (the first among equals)
         double best = cp_segment(px, py, pz, ax, ay, az, abx, aby, abz, d1, d00, q);
         double t[3];
         const double dac = cp_segment(px, py, pz, ax, ay, az, acx, acy, acz, d2, d11, t);

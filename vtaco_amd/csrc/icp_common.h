@@ -1,5 +1,5 @@
-// What icp.hip and point_tree.hip share: the loop's per-problem gate and the moved point.  Everything lives in an unnamed namespace: each
-// translation unit has its own copy.
+// What icp.hip, point_tree.hip and knn.hip share: the loop's per-problem gate, the moved point and the query loader.  Everything lives in
+// an unnamed namespace: each translation unit has its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,6 +14,13 @@ __device__ inline void move_point(const double *T, double x, double y, double z,
     ox = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
     oy = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
     oz = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+}
+
+// query n of problem b among src [B][N][3], moved by T [B][16] when given
+__device__ inline void load_query(const double *src, const double *T, int b, int N, int64_t n, double q[3]) {
+    const double *p = src + ((size_t)b * N + n) * 3;
+    q[0] = p[0]; q[1] = p[1]; q[2] = p[2];
+    if (T) move_point(T + (size_t)b * 16, q[0], q[1], q[2], q[0], q[1], q[2]);
 }
 
 }  // namespace

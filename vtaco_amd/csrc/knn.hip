@@ -16,8 +16,8 @@
 //             broadcast; one partial list per (query, slab) goes to the workspace as [slab][slot][query]; a finish pass (64 lanes per
 //             workgroup) merges the lists in ascending slab order by the same rule, leaving a list at its first entry that is not
 //             taken.  The result does not depend on the slab size
-//   tree      pt_query_kernel's walk without a stack over a PointTree (point_tree.hip), 64 lanes per workgroup: a cell is skipped exactly
-//             when lb > worst, lb the box's lower bound in d2's operation order.  worst is +inf until the list holds k targets.  The
+//   tree      octree_common.h's walk over a PointTree (point_tree.hip), 64 lanes per workgroup: a cell is skipped exactly when
+//             lb > worst, lb = ot_box_d2, the box's lower bound in d2's operation order.  worst is +inf until the list holds k targets.  The
 //             computed lb is <= the computed d2 of every point under the cell (monotone rounding, as in point_tree.hip), so a skipped
 //             cell holds no point with d2 <= worst: none that would be taken, and none that ties with worst at a lower index.  No slack.
 //             Seed leaf, near children first (VTACO_POINT_TREE_WALK), the lane permutation and stats [B][N][2] are point_tree.hip's
@@ -49,7 +49,6 @@ constexpr int KNN_LANES = 64;                   // the walk and the finish pass:
 constexpr int KNN_MIN_CHUNKS = 2;               // chunks per slab at least (vt_nn_points')
 constexpr int KNN_TARGET_BLOCKS = 2048;         // workgroups wanted per launch: 8 per CU
 constexpr int KNN_SWEEPS = 8;                   // Jacobi sweeps (a symmetric 3x3 settles in 4 to 6)
-constexpr int KNN_BOX = OT_BOX;
 constexpr int64_t KNN_MAX = 0x7fffff00;
 
 // one lane's list among TH lanes' in LDS: d [k][TH] doubles, then m [k][TH] int32
@@ -174,82 +173,45 @@ knn_finish_kernel(int N, int M, int k, const char *ws, size_t block_bytes, size_
 // grid (query tiles of 64, B).  perm NULL, or [B][N]: lane i of problem b answers query perm[b][i] (vt_point_tree_lanes)
 template <bool SEED, bool ORDER>
 __global__ void __launch_bounds__(KNN_LANES)
-knn_walk_kernel(const char *trees, size_t stride, size_t pyr_at, size_t box_at, size_t loff_at, size_t list_at, size_t pts_at, OtBase base, int L,
-                const double *src, const double *T, int N, int k, double *d2, int32_t *idx, int32_t *stats, const int32_t *perm) {
+knn_walk_kernel(const char *trees, OtAt tree_at, OtBase base, int L, const double *src, const double *T, int N, int k, double *d2, int32_t *idx,
+                int32_t *stats, const int32_t *perm) {
     const int b = blockIdx.y;
-    const char *tree = trees + (size_t)b * stride;
-    const double *frame = reinterpret_cast<const double *>(tree);
-    const int32_t *pyr = reinterpret_cast<const int32_t *>(tree + pyr_at);
-    const double *boxes = reinterpret_cast<const double *>(tree + box_at);
-    const int32_t *loff = reinterpret_cast<const int32_t *>(tree + loff_at);
-    const int32_t *lst = reinterpret_cast<const int32_t *>(tree + list_at);
-    const double *pts = reinterpret_cast<const double *>(tree + pts_at);
+    const OtView<double> tv = ot_view<double>(trees, tree_at, b);
     const int lane = blockIdx.x * KNN_LANES + threadIdx.x;
     if (lane >= N) return;
     const int n = perm ? perm[(size_t)b * N + lane] : lane;
     double q[3];
-    {
-        const double *p = src + ((size_t)b * N + n) * 3;
-        q[0] = p[0]; q[1] = p[1]; q[2] = p[2];
-        if (T) move_point(T + (size_t)b * 16, q[0], q[1], q[2], q[0], q[1], q[2]);
-    }
-    const double flo[3] = {frame[0], frame[1], frame[2]}, fside = frame[3];
+    load_query(src, T, b, N, n, q);
+    const double flo[3] = {tv.frame[0], tv.frame[1], tv.frame[2]}, fside = tv.frame[3];
     KList<KNN_LANES> list(k, threadIdx.x);
     int n_boxes = 0, n_points = 0, seed_rk = -1;
     // the points of leaf rk in list order
     auto leaf = [&](int rk) {
-        const int o = loff[rk], e = loff[rk + 1];
+        const int o = tv.loff[rk], e = tv.loff[rk + 1];
         for (int t = o; t < e; ++t) {
-            const double *p = pts + (size_t)t * 3;
+            const double *p = tv.payload + (size_t)t * 3;
             const double dx = q[0] - p[0], dy = q[1] - p[1], dz = q[2] - p[2];
             const double d = (dx * dx + dy * dy) + dz * dz;
-            const int m = lst[t];
+            const int m = tv.list[t];
             if (list.takes(d, m)) list.insert(d, m);
         }
         n_points += e - o;
     };
     if (SEED) {
-        seed_rk = pyr[(unsigned)((((int64_t)1 << (3 * L)) - 1) / 7) + ot_code(q[0], q[1], q[2], frame, L)];
+        seed_rk = ot_leaf_of(tv.pyr, tv.frame, L, q);
         if (seed_rk >= 0) leaf(seed_rk);
     }
-    int level = 0;
-    unsigned cell = 0, flip = 0, level_at = 0;                    // level_at = (8^level - 1) / 7; flip: the octant o of every level, 3 bits each
-    for (;;) {
-        const unsigned actual = cell ^ flip;
-        const int rk = pyr[level_at + actual];
-        bool descend = false;
-        if (rk >= 0) {
-            const double *bx = boxes + ((size_t)base.v[level] + rk) * KNN_BOX;
-            double e[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const double lo = bx[a], hi = bx[3 + a];
-                e[a] = q[a] < lo ? lo - q[a] : (q[a] > hi ? q[a] - hi : 0.0);
-            }
-            const double lb = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+    ot_walk(
+        tv.pyr,
+        [&](int level, int rk) {
+            const double lb = ot_box_d2(tv.recs + ((size_t)base.v[level] + rk) * OT_BOX, q);
             ++n_boxes;
-            if (!(lb > list.worst)) {
-                if (level < L) descend = true;
-                else if (rk != seed_rk) leaf(rk);
-            }
-        }
-        if (descend) {
-            unsigned o = 0;
-            if (ORDER) {
-                const double h = fside * (1.0 / (double)(1 << level));
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    const double centre = flo[a] + ((double)ot_gather(actual >> a) + 0.5) * h;
-                    o |= q[a] >= centre ? 1u << a : 0u;
-                }
-            }
-            level_at = level_at * 8 + 1; ++level; cell *= 8; flip = flip * 8 + o;
-        } else {
-            ++cell;
-            while (level > 0 && (cell & 7u) == 0) { cell >>= 3; flip >>= 3; --level; level_at = (level_at - 1) >> 3; }
-            if (level == 0) break;
-        }
-    }
+            if (lb > list.worst) return false;
+            if (level < L) return true;
+            if (rk != seed_rk) leaf(rk);
+            return false;
+        },
+        [&](int level, unsigned actual) { return ot_near_octant<ORDER>(flo, fside, level, actual, q); });
     const size_t at = (size_t)b * N + n;
     list.store(d2 + at * k, idx + at * k, 1);
     if (stats) { stats[2 * at] = n_boxes; stats[2 * at + 1] = n_points; }
@@ -352,8 +314,7 @@ bool knn_sizes_ok(int64_t N, int64_t M, int B) { return N >= 1 && M >= 1 && B >=
 bool knn_k_ok(int k) { return k >= 1 && k <= VT_KNN_MAX_K; }
 bool knn_slab_ok(int slab_points) { return slab_points == 0 || (slab_points > 0 && slab_points % KNN_THREADS == 0); }
 
-typedef void (*KnnWalkFn)(const char *, size_t, size_t, size_t, size_t, size_t, size_t, OtBase, int, const double *, const double *, int, int, double *,
-                          int32_t *, int32_t *, const int32_t *);
+typedef void (*KnnWalkFn)(const char *, OtAt, OtBase, int, const double *, const double *, int, int, double *, int32_t *, int32_t *, const int32_t *);
 const KnnWalkFn KNN_WALK[4] = {knn_walk_kernel<false, false>, knn_walk_kernel<true, false>, knn_walk_kernel<false, true>, knn_walk_kernel<true, true>};
 
 }  // namespace
@@ -400,8 +361,8 @@ int vt_point_tree_knn(const void *tree, size_t tree_bytes, int64_t M, int depth,
     OtBase base;
     for (int l = 0; l <= OT_LEVELS; ++l) base.v[l] = plan.base[l];
     hipLaunchKernelGGL(KNN_WALK[plan.kernel], dim3(blocks_of(N, KNN_LANES), (unsigned)B), dim3(KNN_LANES), knn_lds_bytes(KNN_LANES, k),
-                       (hipStream_t)stream, static_cast<const char *>(tree), plan.stride, plan.pyr, plan.box, plan.loff, plan.list, plan.pts, base,
-                       plan.depth, src, T, (int)N, k, d2, idx, stats, perm);
+                       (hipStream_t)stream, static_cast<const char *>(tree), OtAt{plan.stride, plan.pyr, plan.box, plan.loff, plan.list, plan.pts},
+                       base, plan.depth, src, T, (int)N, k, d2, idx, stats, perm);
     return vt_check(hipGetLastError(), "vt_point_tree_knn");
 }
 

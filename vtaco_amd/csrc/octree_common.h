@@ -1,7 +1,7 @@
-// The octree over items binned by a point, built for B problems by one set of launches: what winding_fast.hip (faces binned by their
-// centroid, B = 1) and point_tree.hip (points binned by themselves) share, and the few pieces closest_point_tree.hip and ray_mesh.hip read
-// a built tree with.  The definitions are DESIGN.md's section "octree_common.h".  Everything lives in an unnamed namespace: each
-// translation unit has its own copy.
+// The octree over items binned by a point.  The build half, for B problems by one set of launches, is what winding_fast.hip (faces binned
+// by their centroid, B = 1) and point_tree.hip (points binned by themselves) share; the query half is what the five kernels that read a
+// built tree share (winding_fast.hip, closest_point_tree.hip, ray_mesh.hip, point_tree.hip, knn.hip).  The definitions are DESIGN.md's
+// section "octree_common.h".  Everything lives in an unnamed namespace: each translation unit has its own copy.
 //   frame     lo = the minimum corner of the source's coordinates, side = their largest extent (1 when 0), n = 2^depth cells per axis,
 //             1 <= depth <= 7.  A coordinate that is not finite sets status bit 1 and is left out
 //   binning   an item lives in the leaf clamp((int)floor((p - lo) / side * n), 0, n - 1) per axis of its point p; cells are numbered in
@@ -10,6 +10,10 @@
 //   pyramid   per level a dense int32 [8^l]: the rank of an occupied cell among its level's occupied cells, or -1
 //   lists     count, scan, fill through an integer cursor, then every item is placed at its rank inside its leaf: ascending index.  The
 //             source's payload of an item is written at the item's place: a leaf's payloads are contiguous
+//   walk      one lane per query, depth first without a stack (ot_walk): the state is (level, cell), "next" is cell + 1 climbing one
+//             level while cell % 8 == 0, "descend" is (level + 1, 8 cell).  The children of a cell are read as k ^ o, o an octant chosen
+//             at the descent (0: Morton order) and kept per level, 3 bits each, in `flip`; "next" and "climb" act on k.  What is done at
+//             an occupied cell and which octant comes first are the caller's two lambdas; OtView and OtSide are what they read
 // A source S is a small struct passed by value to the kernels; it is all that differs between two trees:
 //   coords(), coord(b, i, a)      the coordinates that span the frame of problem b, as doubles, and how many there are per problem
 //   frame_lo(x)                   what is stored for a minimum x (the place where a source may turn a -0.0 into +0.0)
@@ -36,6 +40,8 @@ constexpr int OT_W_TOTAL = 10;
 constexpr int OT_BAD_COORD = 1;                 // status bit: a coordinate that is not finite
 constexpr size_t OT_AUX = 128;                  // bytes per problem: the bounding box as ordered keys (6 u64), at byte 64 lo[3] and side
 constexpr size_t OT_AUX_FRAME = 64;
+constexpr int OT_BOX = 6;                       // doubles per box (48 bytes: 16-byte aligned rows): lo[3], hi[3]
+constexpr size_t OT_SIDE_HEAD = 256;            // bytes in front of a side buffer's boxes; the status word is the first
 
 int64_t cells_of(int l) { return (int64_t)1 << (3 * l); }
 int64_t pyr_off(int l) { return (cells_of(l) - 1) / 7; }     // cells of the levels above l
@@ -130,6 +136,106 @@ __device__ inline T *blk_at(char *blocks, size_t blk, int b, size_t off) { retur
 template <class T>
 __device__ inline const T *blk_at(const char *blocks, size_t blk, int b, size_t off) {
     return reinterpret_cast<const T *>(blocks + (size_t)b * blk + off);
+}
+
+// ---- query: a built tree as a kernel reads it, and the walk ---------------------------------------------------------------------------
+// where a tree keeps its arrays (OtTree's offsets, one set for all problems), and tree b of a buffer through them.  recs: the per-cell
+// records (a point tree's boxes, a face tree's expansions), level l from record base l on; payload: P per item in list order
+struct OtAt { size_t stride, pyr, rec, loff, list, payload; };
+template <class P>
+struct OtView { const double *frame, *recs; const int32_t *pyr, *loff, *list; const P *payload; };
+template <class P>
+__device__ __forceinline__ OtView<P> ot_view(const char *trees, const OtAt &at, int b) {
+    return {blk_at<double>(trees, at.stride, b, 0), blk_at<double>(trees, at.stride, b, at.rec), blk_at<int32_t>(trees, at.stride, b, at.pyr),
+            blk_at<int32_t>(trees, at.stride, b, at.loff), blk_at<int32_t>(trees, at.stride, b, at.list), blk_at<P>(trees, at.stride, b, at.payload)};
+}
+
+// the side buffer closest_point_tree.hip puts beside a face tree and ray_mesh.hip reads too: OT_SIDE_HEAD bytes whose first word is the status,
+// one box per occupied cell (level l from box base.v[l] on, in the order of the tree's records), rec_doubles doubles per face in list
+// order.  state: vt_winding_tree_count's words, validated by vt_winding_tree_layout first
+struct OtSide { size_t box, rec, bytes; OtBase base; };
+struct OtSideView { const double *boxes, *recs; };
+__device__ __forceinline__ OtSideView ot_side_view(const char *side, const OtSide &s) {
+    return {reinterpret_cast<const double *>(side + s.box), reinterpret_cast<const double *>(side + s.rec)};
+}
+void ot_side(int64_t F, int L, const int32_t *state, int rec_doubles, OtSide &s) {
+    int64_t total = 0;
+    for (int l = 0; l < OT_LEVELS; ++l) {
+        s.base.v[l] = (int)total;
+        if (l <= L) total += state[OT_W_COUNT + l];
+    }
+    s.base.v[OT_LEVELS] = (int)total;
+    s.box = OT_SIDE_HEAD;
+    s.rec = s.box + up256((size_t)total * OT_BOX * sizeof(double));
+    s.bytes = s.rec + up256((size_t)F * rec_doubles * sizeof(double));
+}
+
+// the walk of the header comment over the pyramids pyr.  visit(level, rk) is called for every occupied cell (rk >= 0) in the order the
+// cells are read and says whether to descend: it tests, counts and evaluates a leaf itself, and returns false at a leaf.
+// octant(level, actual), called on a descent only, is the 3-bit o the children of cell `actual` are read with: k ^ o
+template <class Visit, class Octant>
+__device__ __forceinline__ void ot_walk(const int32_t *pyr, Visit visit, Octant octant) {
+    int level = 0;
+    unsigned cell = 0, flip = 0, level_at = 0;                    // level_at = (8^level - 1) / 7; flip: the octant o of every level, 3 bits each
+    for (;;) {
+        const unsigned actual = cell ^ flip;
+        const int rk = pyr[level_at + actual];
+        if (rk >= 0 && visit(level, rk)) {
+            const unsigned o = octant(level, actual);
+            level_at = level_at * 8 + 1; ++level; cell *= 8; flip = flip * 8 + o;
+        } else {
+            ++cell;
+            while (level > 0 && (cell & 7u) == 0) { cell >>= 3; flip >>= 3; --level; level_at = (level_at - 1) >> 3; }
+            if (level == 0) break;
+        }
+    }
+}
+
+// near children first: the octant of q about the centre flo_a + (i_a + 0.5) (fside / 2^level) of cell `actual`; 0 when !ORDER
+template <bool ORDER>
+__device__ __forceinline__ unsigned ot_near_octant(const double *flo, double fside, int level, unsigned actual, const double *q) {
+    unsigned o = 0;
+    if (ORDER) {
+        const double h = fside * (1.0 / (double)(1 << level));
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double centre = flo[a] + ((double)ot_gather(actual >> a) + 0.5) * h;
+            o |= q[a] >= centre ? 1u << a : 0u;
+        }
+    }
+    return o;
+}
+
+// the squared distance from q to the box lo[3], hi[3]: e_a = max(lo_a - q_a, 0, q_a - hi_a), that is lo_a - q_a when q_a < lo_a,
+// q_a - hi_a when q_a > hi_a, else 0 (a NaN q_a: 0; an empty box, lo = +inf, hi = -inf: +inf), summed in the operation order of
+// d2 = (dx dx + dy dy) + dz dz.  Without a branch: the box's six doubles are read at once, not one after the other's comparison
+__device__ __forceinline__ double ot_box_d2(const double *box, const double *q) {
+    double e[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        double x = box[a] - q[a];
+        x = x > 0.0 ? x : 0.0;
+        const double y = q[a] - box[3 + a];
+        e[a] = y > x ? y : x;
+    }
+    return (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+}
+
+// the rank of the leaf q is binned into (ot_code: clamped into the frame), or -1 where that leaf is empty
+__device__ __forceinline__ int ot_leaf_of(const int32_t *pyr, const double *frame, int L, const double *q) {
+    return pyr[(unsigned)((((int64_t)1 << (3 * L)) - 1) / 7) + ot_code(q[0], q[1], q[2], frame, L)];
+}
+
+// (m_x + m_y) + m_z, m_a = max(|p_a - lo_a|, |p_a - (lo_a + side)|): no point of the frame is further from p along any axis sum
+__device__ __forceinline__ double ot_frame_reach(const double *frame, const double *p) {
+    double S = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double u = fabs(p[a] - frame[a]), v = fabs(p[a] - (frame[a] + frame[3]));
+        const double m = u > v ? u : v;
+        S = a == 0 ? m : S + m;
+    }
+    return S;
 }
 
 // ---- count: frame, codes, pyramids, list offsets -----------------------------------------------------------------------------------
@@ -356,9 +462,8 @@ ot_rank_kernel(S src, const char *blocks, size_t blk, size_t codes_off, size_t d
     src.payload(b, i, tree + payload_at + at * S::PAYLOAD);
 }
 
-// boxes (lo[3], hi[3], 6 doubles) of the occupied cells of one level from those of their occupied children, the pyramids at
+// boxes (lo[3], hi[3]: OT_BOX doubles) of the occupied cells of one level from those of their occupied children, the pyramids at
 // trees + b stride and the boxes at boxes + b box_stride.  grid (blocks, B)
-constexpr int OT_BOX = 6;
 __global__ void __launch_bounds__(MT_THREADS)
 ot_inner_box_kernel(const char *trees, size_t stride, size_t pyr_at, size_t pyr_child_at, int64_t cells, char *boxes, size_t box_stride,
                     size_t box_child_at, size_t box_level_at) {

@@ -6,16 +6,17 @@
 //             in the leaf it lies in and is copied in list order: a leaf's points are contiguous, ascending by index
 //   boxes     per occupied cell lo[3], hi[3]: a leaf's the min / max of its points, an inner cell's the min / max of its occupied
 //             children.  Minimum and maximum do not round; +0.0 is added on the way out, so a zero is stored as +0.0
-//   query     one lane per query, float64, winding_fast.hip's walk without a stack.  Per occupied cell e_a = lo_a - q_a when
-//             q_a < lo_a, q_a - hi_a when q_a > hi_a, else 0; lb = (e_x e_x + e_y e_y) + e_z e_z, the operation order of
+//   query     one lane per query, float64, octree_common.h's walk.  Per occupied cell lb = ot_box_d2(box, q): e_a = lo_a - q_a when
+//             q_a < lo_a, q_a - hi_a when q_a > hi_a, else 0 (computed there as max(lo_a - q_a, 0, q_a - hi_a): the same value for
+//             every input, without a branch); lb = (e_x e_x + e_y e_y) + e_z e_z, the operation order of
 //             d2 = (dx dx + dy dy) + dz dz, d = q - p.  Rounding is monotone: |fl(q_a - p_a)| >= fl(e_a) >= 0 for every point of the cell,
 //             and products and sums of non-negative values keep the order, so the computed lb is <= the computed d2 of every point
 //             under the cell: the cell is skipped exactly when lb > best, with no slack term.  A leaf's points are taken in list order
 //             on d2 < best || (d2 == best && index < best index): the lowest index among equal minima, as the ascending brute force
 //             gives.  A NaN query makes every comparison false: it visits everything and returns (+inf, -1)
-//   seed      before the walk the query's own clamped leaf, when occupied, is evaluated; the walk tests its box and passes over it
-//   order     the children of a cell are visited as k ^ o, o the octant of the query about the cell's centre
-//             lo_a + (i_a + 0.5) (side / 2^level): near children first
+//   seed      before the walk the query's own clamped leaf (ot_leaf_of), when occupied, is evaluated; the walk tests its box and passes
+//             over it
+//   order     near children first: ot_near_octant, the octant of the query about the cell's centre
 //   lanes     optionally lane i answers query perm[i], perm the queries in Morton order of the tree's leaves (octree_common.h's count /
 //             scan / fill with PtLaneSource, per call): a wave's lanes then walk neighbouring cells.  Outputs stay in query order; no result depends on perm
 // Seed and order change which cells are skipped, never a result.  VTACO_POINT_TREE_WALK = plain | seed | order | seed+order picks the
@@ -35,7 +36,6 @@
 
 namespace {
 
-constexpr int PT_BOX = OT_BOX;                  // doubles per cell record: the box lo[3], hi[3]
 constexpr int64_t PT_MAX_M = MT_MAX_F;
 constexpr int64_t PT_MAX_N = 0x7fffff00;
 
@@ -60,11 +60,7 @@ struct PtLaneSource {
     const double *src, *T;
     int N;
     __host__ __device__ int items() const { return N; }
-    __device__ void point(int b, int64_t n, double p[3]) const {
-        const double *q = src + ((size_t)b * N + n) * 3;
-        p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
-        if (T) move_point(T + (size_t)b * 16, p[0], p[1], p[2], p[0], p[1], p[2]);
-    }
+    __device__ void point(int b, int64_t n, double p[3]) const { load_query(src, T, b, N, n, p); }
 };
 
 // the layout of B trees of boxes; a point tree has an occupied cell at every level of every problem
@@ -72,7 +68,7 @@ bool pt_tree(int64_t M, int L, int B, const int32_t *state, OtTree &t) {
     for (int b = 0; b < B; ++b)
         for (int l = 0; l <= L; ++l)
             if (state[(size_t)b * OT_STATE + OT_W_COUNT + l] < 1) return false;
-    return ot_tree(M, L, B, state, PT_BOX, PtSource::PAYLOAD, t);
+    return ot_tree(M, L, B, state, OT_BOX, PtSource::PAYLOAD, t);
 }
 
 // ---- boxes -----------------------------------------------------------------------------------------------------------------------------
@@ -96,21 +92,20 @@ pt_leaf_box_kernel(char *trees, size_t stride, size_t pyr_leaf_at, int64_t cells
             hi[a] = x > hi[a] ? x : hi[a];
         }
     }
-    double *bx = reinterpret_cast<double *>(tree + box_leaf_at) + (size_t)rk * PT_BOX;
+    double *bx = reinterpret_cast<double *>(tree + box_leaf_at) + (size_t)rk * OT_BOX;
 #pragma unroll
     for (int a = 0; a < 3; ++a) { bx[a] = lo[a] + 0.0; bx[3 + a] = hi[a] + 0.0; }
 }
 
 // ---- query ---------------------------------------------------------------------------------------------------------------------------
 // the points of leaf rk in list order; the tie rule is explicit: the walk does not meet points in ascending order
-__device__ inline int pt_leaf(const int32_t *loff, const int32_t *list, const double *pts, int rk, double qx, double qy, double qz, double &best,
-                              int &best_m) {
-    const int o = loff[rk], e = loff[rk + 1];
+__device__ inline int pt_leaf(const OtView<double> &tv, int rk, const double *q, double &best, int &best_m) {
+    const int o = tv.loff[rk], e = tv.loff[rk + 1];
     for (int t = o; t < e; ++t) {
-        const double *p = pts + (size_t)t * 3;
-        const double dx = qx - p[0], dy = qy - p[1], dz = qz - p[2];
+        const double *p = tv.payload + (size_t)t * 3;
+        const double dx = q[0] - p[0], dy = q[1] - p[1], dz = q[2] - p[2];
         const double d = (dx * dx + dy * dy) + dz * dz;
-        const int m = list[t];
+        const int m = tv.list[t];
         if (d < best || (d == best && m < best_m)) { best = d; best_m = m; }
     }
     return e - o;
@@ -119,71 +114,34 @@ __device__ inline int pt_leaf(const int32_t *loff, const int32_t *list, const do
 // grid (query tiles, B).  perm NULL, or [B][N]: lane i of problem b answers query perm[b][i] (vt_point_tree_lanes)
 template <bool SEED, bool ORDER>
 __global__ void __launch_bounds__(MT_THREADS)
-pt_query_kernel(const char *trees, size_t stride, size_t pyr_at, size_t box_at, size_t loff_at, size_t list_at, size_t pts_at, OtBase base, int L,
-                const double *src, const double *T, int N, double *d2, int32_t *idx, int32_t *stats, const int32_t *perm, Gate gate) {
+pt_query_kernel(const char *trees, OtAt tree_at, OtBase base, int L, const double *src, const double *T, int N, double *d2, int32_t *idx,
+                int32_t *stats, const int32_t *perm, Gate gate) {
     const int b = blockIdx.y;
     if (frozen(gate, b)) return;
-    const char *tree = trees + (size_t)b * stride;
-    const double *frame = reinterpret_cast<const double *>(tree);
-    const int32_t *pyr = reinterpret_cast<const int32_t *>(tree + pyr_at);
-    const double *boxes = reinterpret_cast<const double *>(tree + box_at);
-    const int32_t *loff = reinterpret_cast<const int32_t *>(tree + loff_at);
-    const int32_t *list = reinterpret_cast<const int32_t *>(tree + list_at);
-    const double *pts = reinterpret_cast<const double *>(tree + pts_at);
+    const OtView<double> tv = ot_view<double>(trees, tree_at, b);
     const int lane = blockIdx.x * MT_THREADS + threadIdx.x;
     if (lane >= N) return;
     const int n = perm ? perm[(size_t)b * N + lane] : lane;
     double q[3];
-    {
-        const double *p = src + ((size_t)b * N + n) * 3;
-        q[0] = p[0]; q[1] = p[1]; q[2] = p[2];
-        if (T) move_point(T + (size_t)b * 16, q[0], q[1], q[2], q[0], q[1], q[2]);
-    }
-    const double flo[3] = {frame[0], frame[1], frame[2]}, fside = frame[3];
+    load_query(src, T, b, N, n, q);
+    const double flo[3] = {tv.frame[0], tv.frame[1], tv.frame[2]}, fside = tv.frame[3];
     double best = __builtin_inf();
     int best_m = -1, n_boxes = 0, n_points = 0, seed_rk = -1;
     if (SEED) {
-        seed_rk = pyr[(unsigned)((((int64_t)1 << (3 * L)) - 1) / 7) + ot_code(q[0], q[1], q[2], frame, L)];
-        if (seed_rk >= 0) n_points += pt_leaf(loff, list, pts, seed_rk, q[0], q[1], q[2], best, best_m);
+        seed_rk = ot_leaf_of(tv.pyr, tv.frame, L, q);
+        if (seed_rk >= 0) n_points += pt_leaf(tv, seed_rk, q, best, best_m);
     }
-    int level = 0;
-    unsigned cell = 0, flip = 0, level_at = 0;                    // level_at = (8^level - 1) / 7; flip: the octant o of every level, 3 bits each
-    for (;;) {
-        const unsigned actual = cell ^ flip;
-        const int rk = pyr[level_at + actual];
-        bool descend = false;
-        if (rk >= 0) {
-            const double *bx = boxes + ((size_t)base.v[level] + rk) * PT_BOX;
-            double e[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const double lo = bx[a], hi = bx[3 + a];
-                e[a] = q[a] < lo ? lo - q[a] : (q[a] > hi ? q[a] - hi : 0.0);
-            }
-            const double lb = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+    ot_walk(
+        tv.pyr,
+        [&](int level, int rk) {
+            const double lb = ot_box_d2(tv.recs + ((size_t)base.v[level] + rk) * OT_BOX, q);
             ++n_boxes;
-            if (!(lb > best)) {
-                if (level < L) descend = true;
-                else if (rk != seed_rk) n_points += pt_leaf(loff, list, pts, rk, q[0], q[1], q[2], best, best_m);
-            }
-        }
-        if (descend) {
-            unsigned o = 0;
-            if (ORDER) {
-                const double h = fside * (1.0 / (double)(1 << level));
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    const double centre = flo[a] + ((double)ot_gather(actual >> a) + 0.5) * h;
-                    o |= q[a] >= centre ? 1u << a : 0u;
-                }
-            }
-            level_at = level_at * 8 + 1; ++level; cell *= 8; flip = flip * 8 + o;
-        } else {
-            ++cell;
-            while (level > 0 && (cell & 7u) == 0) { cell >>= 3; flip >>= 3; --level; level_at = (level_at - 1) >> 3; }
-            if (level == 0) break;
-        }
-    }
+            if (lb > best) return false;
+            if (level < L) return true;
+            if (rk != seed_rk) n_points += pt_leaf(tv, rk, q, best, best_m);
+            return false;
+        },
+        [&](int level, unsigned actual) { return ot_near_octant<ORDER>(flo, fside, level, actual, q); });
     const size_t at = (size_t)b * N + n;
     d2[at] = best;
     idx[at] = best_m;
@@ -193,8 +151,7 @@ pt_query_kernel(const char *trees, size_t stride, size_t pyr_at, size_t box_at, 
 bool pt_sizes_ok(int64_t M, int B) { return M >= 1 && M <= PT_MAX_M && B >= 1 && B <= 65535; }
 bool pt_depth_ok(int depth) { return depth >= 1 && depth <= VT_WN_MAX_DEPTH; }
 
-typedef void (*PtQueryFn)(const char *, size_t, size_t, size_t, size_t, size_t, size_t, OtBase, int, const double *, const double *, int, double *,
-                          int32_t *, int32_t *, const int32_t *, Gate);
+typedef void (*PtQueryFn)(const char *, OtAt, OtBase, int, const double *, const double *, int, double *, int32_t *, int32_t *, const int32_t *, Gate);
 const PtQueryFn PT_QUERY[4] = {pt_query_kernel<false, false>, pt_query_kernel<true, false>, pt_query_kernel<false, true>, pt_query_kernel<true, true>};
 
 }  // namespace
@@ -245,8 +202,8 @@ void pt_query_enqueue(const PtQueryPlan &plan, const void *tree, const double *s
     OtBase base;
     for (int l = 0; l <= OT_LEVELS; ++l) base.v[l] = plan.base[l];
     hipLaunchKernelGGL(PT_QUERY[plan.kernel], dim3(blocks_of(plan.N, MT_THREADS), (unsigned)plan.B), dim3(MT_THREADS), 0, (hipStream_t)stream,
-                       static_cast<const char *>(tree), plan.stride, plan.pyr, plan.box, plan.loff, plan.list, plan.pts, base, plan.depth, src, T,
-                       (int)plan.N, d2, idx, stats, perm, Gate{done, iter, it});
+                       static_cast<const char *>(tree), OtAt{plan.stride, plan.pyr, plan.box, plan.loff, plan.list, plan.pts}, base, plan.depth,
+                       src, T, (int)plan.N, d2, idx, stats, perm, Gate{done, iter, it});
 }
 
 extern "C" {
@@ -293,11 +250,11 @@ int vt_point_tree_build(const double *dst, int64_t M, int B, int depth, const in
     const unsigned nb = (unsigned)B;
     const int64_t leaf = cells_of(depth);
     hipLaunchKernelGGL(pt_leaf_box_kernel, dim3(blocks_of(leaf, MT_THREADS), nb), dim3(MT_THREADS), 0, st, tr, t.stride,
-                       t.pyr + (size_t)pyr_off(depth) * 4, leaf, t.loff, t.payload, t.rec + (size_t)t.base.v[depth] * PT_BOX * sizeof(double));
+                       t.pyr + (size_t)pyr_off(depth) * 4, leaf, t.loff, t.payload, t.rec + (size_t)t.base.v[depth] * OT_BOX * sizeof(double));
     for (int l = depth - 1; l >= 0; --l)
         hipLaunchKernelGGL(ot_inner_box_kernel, dim3(blocks_of(cells_of(l), MT_THREADS), nb), dim3(MT_THREADS), 0, st, (const char *)tr, t.stride,
                            t.pyr + (size_t)pyr_off(l) * 4, t.pyr + (size_t)pyr_off(l + 1) * 4, cells_of(l), tr, t.stride,
-                           t.rec + (size_t)t.base.v[l + 1] * PT_BOX * sizeof(double), t.rec + (size_t)t.base.v[l] * PT_BOX * sizeof(double));
+                           t.rec + (size_t)t.base.v[l + 1] * OT_BOX * sizeof(double), t.rec + (size_t)t.base.v[l] * OT_BOX * sizeof(double));
     return vt_check(hipGetLastError(), "vt_point_tree_build");
 }
 

@@ -10,16 +10,15 @@
 //                       equal s give the lowest face index.  No atomic on a result: bit-reproducible, independent of the slab size
 //   vt_ray_tree_query   the same s and face from a walk of winding_fast.hip's octree with closest_point_tree.hip's side buffer (one tight
 //                       box per occupied cell, the kind of every face in list order); the corners come from the tree's F x 9 f32 in list
-//                       order.  One lane per ray, closest_point_tree.hip's walk without a stack: the state is (level, cell), "next" is
-//                       cell + 1 climbing while cell % 8 == 0, "descend" is (level + 1, 8 cell).  An occupied cell and everything under it
-//                       is skipped when the segment [t_min, min(t_max, best)] misses the cell's box grown by E:
+//                       order.  One lane per ray, octree_common.h's walk.  An occupied cell and everything under it is skipped when
+//                       the segment [t_min, min(t_max, best)] misses the cell's box grown by E:
 //                         x0_a = (lo_a - o_a) - E, x1_a = (hi_a - o_a) + E;  d_a == 0: skipped when x0_a > 0 or x1_a < 0;  otherwise
 //                         (near_a, far_a) = (x0_a, x1_a) (1 / d_a), exchanged when d_a < 0;  enter = t_min, exit = min(t_max, best),
 //                         enter = near_a where near_a > enter, exit = far_a where far_a < exit;  skipped when enter > exit
 //                       Every comparison is false for a NaN: a NaN constrains nothing and skips nothing.  A leaf that is not skipped runs
 //                       rf_face over its list in list order and takes a face on
 //                       s < best || (s == best && face < best_face): the walk does not meet faces in ascending order
-//   E                   2^-40 S, S = (m_x + m_y) + m_z, m_a = max(|o_a - lo_a|, |o_a - (lo_a + side)|) over the tree's frame: S bounds
+//   E                   2^-40 S, S = ot_frame_reach = (m_x + m_y) + m_z, m_a = max(|o_a - lo_a|, |o_a - (lo_a + side)|): S bounds
 //                       |corner_a - o_a| of every face, and the point o + s d of a computed hit lies within (19 + 12 k) u S of the face's
 //                       box, u = 2^-53, k the face's aspect seen along the ray (DESIGN.md derives it); 2^-40 = 8192 u covers k <= 681
 //   order               the children of a cell are visited as k ^ o, o_a = (d_a < 0): near children first, one o for the whole ray
@@ -39,6 +38,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "closest_point_face.h"
 #include "mesh_common.h"
 #include "octree_common.h"
 #include "ray_face.h"
@@ -52,9 +52,6 @@ constexpr int RM_MIN_CHUNKS = 2;                // chunks per slab at least: eve
 constexpr int RM_TARGET_BLOCKS = 2048;          // workgroups wanted per launch: 8 per CU
 constexpr size_t RM_HEAD = 256;                 // bytes in front of the workspace; the call's status word is the first
 constexpr int RM_BAD_INDEX = 1;                 // status bit (closest_point_face.h's CP_BAD_INDEX)
-constexpr int RT_BOX = 6;                       // closest_point_tree.hip's side buffer: doubles per box, doubles per face record, the kind's slot
-constexpr int RT_CP_REC = 14;
-constexpr int RT_CP_KIND = 12;
 constexpr double RT_SLACK = 0x1p-40;
 
 struct RmPlan { int slab_faces, slabs; size_t rec_off, ps_off, pface_off, bytes; };
@@ -183,15 +180,14 @@ __device__ inline void rt_corners(const float *tri, int t, double p[9]) {
 }
 
 // rf_face over the list of leaf rk, in list order; the tie rule is explicit
-__device__ inline int rt_leaf(const int32_t *loff, const int32_t *list, const float *tri, const double *recs, int rk, const RfRay &ray, double t_min,
-                              double t_max, RtBest &best) {
-    const int o = loff[rk], e = loff[rk + 1];
+__device__ inline int rt_leaf(const OtView<float> &tv, const double *recs, int rk, const RfRay &ray, double t_min, double t_max, RtBest &best) {
+    const int o = tv.loff[rk], e = tv.loff[rk + 1];
     for (int t = o; t < e; ++t) {
-        if (recs[(size_t)t * RT_CP_REC + RT_CP_KIND] == 2.0) continue;
+        if (recs[(size_t)t * CP_REC + CP_KIND] == CP_SKIP) continue;
         double p[9], s;
-        rt_corners(tri, t, p);
+        rt_corners(tv.payload, t, p);
         if (!rf_face(ray, p, p + 3, p + 6, t_min, t_max, s)) continue;
-        const int f = list[t];
+        const int f = tv.list[t];
         if (s < best.s || (s == best.s && f < best.face)) { best.s = s; best.face = f; best.slot = t; }
     }
     return e - o;
@@ -199,18 +195,12 @@ __device__ inline int rt_leaf(const int32_t *loff, const int32_t *list, const fl
 
 template <bool ORDER>
 __global__ void __launch_bounds__(MT_THREADS)
-rt_query_kernel(const char *tree, size_t pyr_at, size_t loff_at, size_t list_at, size_t tri_at, const char *side, size_t box_at, size_t rec_at,
-                OtBase base, int L, const double *origins, int64_t per_origin, const double *dirs, int64_t N, double t_min, double t_max,
-                double *s_out, int32_t *face, double *bary, int32_t *stats) {
+rt_query_kernel(const char *tree, OtAt tree_at, const char *side, OtSide sd, int L, const double *origins, int64_t per_origin, const double *dirs,
+                int64_t N, double t_min, double t_max, double *s_out, int32_t *face, double *bary, int32_t *stats) {
     const int64_t n = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
     if (n >= N) return;
-    const double *frame = reinterpret_cast<const double *>(tree);
-    const int32_t *pyr = reinterpret_cast<const int32_t *>(tree + pyr_at);
-    const int32_t *loff = reinterpret_cast<const int32_t *>(tree + loff_at);
-    const int32_t *list = reinterpret_cast<const int32_t *>(tree + list_at);
-    const float *tri = reinterpret_cast<const float *>(tree + tri_at);
-    const double *boxes = reinterpret_cast<const double *>(side + box_at);
-    const double *recs = reinterpret_cast<const double *>(side + rec_at);
+    const OtView<float> tv = ot_view<float>(tree, tree_at, 0);
+    const OtSideView sv = ot_side_view(side, sd);
     const double *op = origins + 3 * (n / per_origin), *dp = dirs + 3 * n;
     const double o[3] = {op[0], op[1], op[2]}, d[3] = {dp[0], dp[1], dp[2]};
     RfRay ray;
@@ -218,24 +208,18 @@ rt_query_kernel(const char *tree, size_t pyr_at, size_t loff_at, size_t list_at,
     RtBest best = {__builtin_inf(), -1, -1};
     int n_boxes = 0, n_faces = 0;
     if (ray.ok) {
-        double S = 0.0, inv[3];
+        double inv[3];
         unsigned oct = 0;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            const double u = fabs(o[a] - frame[a]), v = fabs(o[a] - (frame[a] + frame[3]));
-            const double m = u > v ? u : v;
-            S = a == 0 ? m : S + m;
             inv[a] = 1.0 / d[a];
             if (ORDER) oct |= d[a] < 0.0 ? 1u << a : 0u;
         }
-        const double E = S * RT_SLACK;
-        int level = 0;
-        unsigned cell = 0, flip = 0, level_at = 0;                // level_at = (8^level - 1) / 7; flip: o at every level, 3 bits each
-        for (;;) {
-            const int rk = pyr[level_at + (cell ^ flip)];
-            bool descend = false;
-            if (rk >= 0) {
-                const double *b = boxes + ((size_t)base.v[level] + rk) * RT_BOX;
+        const double E = ot_frame_reach(tv.frame, o) * RT_SLACK;
+        ot_walk(
+            tv.pyr,
+            [&](int level, int rk) {
+                const double *b = sv.boxes + ((size_t)sd.base.v[level] + rk) * OT_BOX;
                 double enter = t_min, exit = best.s < t_max ? best.s : t_max;
                 bool skip = false;
 #pragma unroll
@@ -252,19 +236,12 @@ rt_query_kernel(const char *tree, size_t pyr_at, size_t loff_at, size_t list_at,
                 }
                 skip = skip || enter > exit;
                 ++n_boxes;
-                if (!skip) {
-                    if (level < L) descend = true;
-                    else n_faces += rt_leaf(loff, list, tri, recs, rk, ray, t_min, t_max, best);
-                }
-            }
-            if (descend) {
-                level_at = level_at * 8 + 1; ++level; cell *= 8; flip = flip * 8 + oct;
-            } else {
-                ++cell;
-                while (level > 0 && (cell & 7u) == 0) { cell >>= 3; flip >>= 3; --level; level_at = (level_at - 1) >> 3; }
-                if (level == 0) break;
-            }
-        }
+                if (skip) return false;
+                if (level < L) return true;
+                n_faces += rt_leaf(tv, sv.recs, rk, ray, t_min, t_max, best);
+                return false;
+            },
+            [&](int, unsigned) { return oct; });
     }
     s_out[n] = best.s;
     face[n] = best.face;
@@ -272,7 +249,7 @@ rt_query_kernel(const char *tree, size_t pyr_at, size_t loff_at, size_t list_at,
         double w[3] = {__builtin_nan(""), __builtin_nan(""), __builtin_nan("")};
         if (best.slot >= 0) {
             double p[9], s, uvw[4];
-            rt_corners(tri, best.slot, p);
+            rt_corners(tv.payload, best.slot, p);
             if (rf_face(ray, p, p + 3, p + 6, t_min, t_max, s, uvw)) { w[0] = uvw[0] / uvw[3]; w[1] = uvw[1] / uvw[3]; w[2] = uvw[2] / uvw[3]; }
         }
         bary[3 * n] = w[0]; bary[3 * n + 1] = w[1]; bary[3 * n + 2] = w[2];
@@ -356,26 +333,21 @@ int vt_ray_tree_query(const void *tree, size_t tree_bytes, const void *side, siz
     const char *who = "vt_ray_tree_query: bad argument (a mesh needs F > 0, rays_per_origin >= 1)";
     if (!tree || !side || F <= 0 || !state_host) return vt_fail(VT_ERR_INVALID, who);
     if (int rc = rm_ray_args(who, origins, rays_per_origin, dirs, N, s, face)) return rc;
-    size_t off[6], soff[3];
+    size_t off[6];
     if (int rc = vt_winding_tree_layout(F, depth, state_host, off)) return rc;
-    if (int rc = vt_closest_tree_layout(F, depth, state_host, soff)) return rc;
-    if (tree_bytes < off[5] || side_bytes < soff[2]) return vt_fail(VT_ERR_WORKSPACE, "vt_ray_tree_query: tree or side buffer too small");
+    OtSide sd;
+    ot_side(F, depth, state_host, CP_REC, sd);
+    if (tree_bytes < off[5] || side_bytes < sd.bytes) return vt_fail(VT_ERR_WORKSPACE, "vt_ray_tree_query: tree or side buffer too small");
     if (N == 0) return 0;
-    OtBase base;
-    int64_t total = 0;
-    for (int l = 0; l <= OT_LEVELS; ++l) {
-        base.v[l] = (int)total;
-        if (l <= depth) total += state_host[1 + l];
-    }
     const char *walk = getenv("VTACO_RAY_TREE_WALK");
     auto kernel = rt_query_kernel<true>;
     if (walk && walk[0]) {
         if (!strcmp(walk, "plain")) kernel = rt_query_kernel<false>;
         else if (strcmp(walk, "order")) return vt_fail(VT_ERR_INVALID, "vt_ray_tree_query: VTACO_RAY_TREE_WALK must be plain or order");
     }
-    hipLaunchKernelGGL(kernel, dim3(blocks_of(N, MT_THREADS)), dim3(MT_THREADS), 0, (hipStream_t)stream, static_cast<const char *>(tree), off[0], off[2],
-                       off[3], off[4], static_cast<const char *>(side), soff[0], soff[1], base, depth, origins, rays_per_origin, dirs, N, t_min, t_max,
-                       s, face, bary, stats);
+    hipLaunchKernelGGL(kernel, dim3(blocks_of(N, MT_THREADS)), dim3(MT_THREADS), 0, (hipStream_t)stream, static_cast<const char *>(tree),
+                       OtAt{0, off[0], off[1], off[2], off[3], off[4]}, static_cast<const char *>(side), sd, depth, origins, rays_per_origin, dirs, N,
+                       t_min, t_max, s, face, bary, stats);
     return vt_check(hipGetLastError(), "vt_ray_tree_query");
 }
 

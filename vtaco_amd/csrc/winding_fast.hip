@@ -10,9 +10,8 @@
 //   record    36 doubles per occupied cell: p, r, N0, M1[j][i], M2[jk][i] (jk = 00 01 02 11 12 22), total area, face count.  A leaf is
 //             summed by one thread over its list, an inner cell by one thread over its children in Morton order: no float atomic, one
 //             order, the records are equal from run to run and equal to the restatement's bit for bit
-//   query     one lane per query, depth first without a stack: the state is (level, cell), "next" is cell + 1 climbing while
-//             cell % 8 == 0, "descend" is (level + 1, 8 cell).  A cell with |q - p|^2 > accuracy^2 r^2 adds its expansion, a leaf that is
-//             not accepted the Van Oosterom-Strackee solid angles of its faces in list order; w = (far + near) / 4 pi
+//   query     one lane per query, octree_common.h's walk in Morton order.  A cell with |q - p|^2 > accuracy^2 r^2 adds its expansion, a
+//             leaf that is not accepted the Van Oosterom-Strackee solid angles of its faces in list order; w = (far + near) / 4 pi
 // No launch function allocates, copies to the host or waits: the one host read of a build (the occupied cells per level and the status
 // word, the first 64 bytes of vt_winding_tree_count's workspace: octree_common.h's state words) is the caller's, between the two calls.
 #include <hip/hip_runtime.h>
@@ -258,51 +257,47 @@ __device__ inline double wf_expansion(const double *c, double rx, double ry, dou
 // is for, and 5 to 16 % faster on small meshes, where the exact kernel wins anyway.
 template <bool SKIP>
 __global__ void __launch_bounds__(MT_THREADS)
-wf_query_kernel(const char *tree, size_t pyr_at, size_t rec_at, size_t loff_at, size_t tri_at, int L, const float *pts, int64_t N, double beta2,
-                int order, void *out, int out_f64, int32_t *stats) {
+wf_query_kernel(const char *tree, OtAt tree_at, int L, const float *pts, int64_t N, double beta2, int order, void *out, int out_f64, int32_t *stats) {
     const int64_t n = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x;
     if (n >= N) return;
-    const int32_t *pyr = reinterpret_cast<const int32_t *>(tree + pyr_at);
-    const int32_t *rec_base = reinterpret_cast<const int32_t *>(tree + 64);
-    const double *recs = reinterpret_cast<const double *>(tree + rec_at);
-    const int32_t *loff = reinterpret_cast<const int32_t *>(tree + loff_at);
-    const float *tri = reinterpret_cast<const float *>(tree + tri_at);
+    const OtView<float> tv = ot_view<float>(tree, tree_at, 0);
+    const int32_t *pyr = tv.pyr, *rec_base = reinterpret_cast<const int32_t *>(tree + 64);
     const double px = pts[3 * n], py = pts[3 * n + 1], pz = pts[3 * n + 2];
     double far = 0.0, near = 0.0;
     int accepted = 0, exact = 0;
-    int level = 0;
-    unsigned cell = 0, level_at = 0;                              // level_at = (8^level - 1) / 7
-    u64 todo = 0;                                                 // SKIP: byte l = the occupied children not yet visited at level l
-    for (;;) {
-        const int rk = pyr[level_at + cell];
-        bool descend = false;
-        if (rk >= 0) {
-            const double *c = recs + ((size_t)rec_base[level] + rk) * WF_REC;
-            const double rx = c[0] - px, ry = c[1] - py, rz = c[2] - pz, r = c[3];
-            const double d2 = (rx * rx + ry * ry) + rz * rz;
-            if (d2 > beta2 * (r * r)) {
-                far = far + wf_expansion(c, rx, ry, rz, d2, order);
-                ++accepted;
-            } else if (level < L) {
-                descend = true;
-            } else {
-                const int o = loff[rk], e = loff[rk + 1];
-                exact += e - o;
-                for (int t = o; t < e; ++t) {
-                    const float *v = tri + (size_t)t * 9;
-                    const double ax = v[0] - px, ay = v[1] - py, az = v[2] - pz;
-                    const double bx = v[3] - px, by = v[4] - py, bz = v[5] - pz;
-                    const double cx = v[6] - px, cy = v[7] - py, cz = v[8] - pz;
-                    const double la = sqrt(ax * ax + ay * ay + az * az), lb = sqrt(bx * bx + by * by + bz * bz), lc = sqrt(cx * cx + cy * cy + cz * cz);
-                    const double num = ax * (by * cz - bz * cy) + ay * (bz * cx - bx * cz) + az * (bx * cy - by * cx);
-                    const double den = la * lb * lc + (ax * bx + ay * by + az * bz) * lc + (bx * cx + by * cy + bz * cz) * la +
-                                       (cx * ax + cy * ay + cz * az) * lb;
-                    near = near + 2.0 * atan2(num, den);
-                }
-            }
+    // an occupied cell: its expansion, or a descent, or at a leaf its faces
+    auto visit = [&](int level, int rk) {
+        const double *c = tv.recs + ((size_t)rec_base[level] + rk) * WF_REC;
+        const double rx = c[0] - px, ry = c[1] - py, rz = c[2] - pz, r = c[3];
+        const double d2 = (rx * rx + ry * ry) + rz * rz;
+        if (d2 > beta2 * (r * r)) {
+            far = far + wf_expansion(c, rx, ry, rz, d2, order);
+            ++accepted;
+            return false;
         }
-        if (SKIP) {
-            if (descend) {
+        if (level < L) return true;
+        const int o = tv.loff[rk], e = tv.loff[rk + 1];
+        exact += e - o;
+        for (int t = o; t < e; ++t) {
+            const float *v = tv.payload + (size_t)t * 9;
+            const double ax = v[0] - px, ay = v[1] - py, az = v[2] - pz;
+            const double bx = v[3] - px, by = v[4] - py, bz = v[5] - pz;
+            const double cx = v[6] - px, cy = v[7] - py, cz = v[8] - pz;
+            const double la = sqrt(ax * ax + ay * ay + az * az), lb = sqrt(bx * bx + by * by + bz * bz), lc = sqrt(cx * cx + cy * cy + cz * cz);
+            const double num = ax * (by * cz - bz * cy) + ay * (bz * cx - bx * cz) + az * (bx * cy - by * cx);
+            const double den = la * lb * lc + (ax * bx + ay * by + az * bz) * lc + (bx * cx + by * cy + bz * cz) * la +
+                               (cx * ax + cy * ay + cz * az) * lb;
+            near = near + 2.0 * atan2(num, den);
+        }
+        return false;
+    };
+    if (SKIP) {
+        int level = 0;
+        unsigned cell = 0, level_at = 0;                          // level_at = (8^level - 1) / 7
+        u64 todo = 0;                                             // byte l = the occupied children not yet visited at level l
+        for (;;) {
+            const int rk = pyr[level_at + cell];
+            if (rk >= 0 && visit(level, rk)) {
                 level_at = level_at * 8 + 1; ++level; cell *= 8;
                 const int32_t *ch = pyr + level_at + cell;
                 unsigned occ = 0;
@@ -316,13 +311,9 @@ wf_query_kernel(const char *tree, size_t pyr_at, size_t rec_at, size_t loff_at, 
             const unsigned k = (unsigned)__ffs((int)rest) - 1u;
             todo &= ~((u64)1 << (8 * level + k));
             cell = (cell & ~7u) | k;
-        } else if (descend) {
-            level_at = level_at * 8 + 1; ++level; cell *= 8;
-        } else {
-            ++cell;
-            while (level > 0 && (cell & 7u) == 0) { cell >>= 3; --level; level_at = (level_at - 1) >> 3; }
-            if (level == 0) break;
         }
+    } else {
+        ot_walk(pyr, visit, [](int, unsigned) { return 0u; });
     }
     const double w = (far + near) / (4.0 * 3.14159265358979323846);
     if (out_f64) static_cast<double *>(out)[n] = w;
@@ -411,8 +402,8 @@ int vt_winding_tree_query(const void *tree, size_t tree_bytes, int64_t F, int de
     if (tree_bytes < t.bytes) return vt_fail(VT_ERR_WORKSPACE, "vt_winding_tree_query: tree too small");
     const char *walk = getenv("VTACO_WINDING_WALK");
     auto kernel = walk && !strcmp(walk, "skip") ? wf_query_kernel<true> : wf_query_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(blocks_of(N, MT_THREADS)), dim3(MT_THREADS), 0, st, static_cast<const char *>(tree), t.pyr, t.rec, t.loff,
-                       t.payload, depth, pts, N, accuracy * accuracy, order, out, out_f64, stats);
+    hipLaunchKernelGGL(kernel, dim3(blocks_of(N, MT_THREADS)), dim3(MT_THREADS), 0, st, static_cast<const char *>(tree),
+                       OtAt{t.stride, t.pyr, t.rec, t.loff, t.list, t.payload}, depth, pts, N, accuracy * accuracy, order, out, out_f64, stats);
     return vt_check(hipGetLastError(), "vt_winding_tree_query");
 }
 
